@@ -10,12 +10,16 @@ all-reduce of the flat 236 B/Gaussian buffer; `--exchange factored`, the default
 colour gradients + all-reduce of the 44 B/Gaussian geometry block, gaustudio_amd/parallel.py).
 value = N * V * H * W / step_time.
 
-    python bench.py                                  # N=1, C3: static camera (headline) + rotating-camera block + fast_exp block
+    python bench.py                                  # N=1, C3: the headline step alone (set up, settle, warm up, K timed steps)
+    python bench.py --full                           # + stage times, roofline, rotating-camera / fast_exp / ... blocks, CPU baseline
+    python bench.py --dump-outputs DIR               # + the last timed step's outputs and gradients as DIR/<name>.npy
     python bench.py --workload C3-extract            # BASELINE config 3 as worded: depth+normal render (gs-extract-mesh path)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W [--views-per-rank V]
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant north-star kernel (composite_fwd):
+Prints ONE JSON line on rank 0.  A plain run carries the headline (`metric`, `value`, `unit`, `ms_per_step`, ...), the
+configuration and, at N > 1, the `comm` block of its own timed steps.  Everything below takes runs of its own and is
+reported with `--full` only.  `roofline` is for the dominant north-star kernel (composite_fwd):
 algorithmic bytes R*44 + T*8 + H*W*32 (+ H*W*8 training aux) over its mean duration,
 measured with HIP events on the launch stream during the timed steps.  `cpu_baseline` is the CPU
 oracle (a C restatement of the reference kernels -- the reference itself has no CPU renderer) timed on
@@ -62,6 +66,9 @@ WORKLOADS = {
     "C4-inside": (5_000_000, 1297, 840, 3, "C4-inside: 5M Gaussians in a ball of radius 6 (garden stand-in), one 1297x840 view from a camera "
                                            "INSIDE the scene (ring of radius 2.5 looking through the centre), SH degree 3, fwd+bwd"),
 }
+EXTRACT_METRIC = "Mpixels/s depth+normal render + TSDF integrate @1M Gaussians 1920x1080 (gs-extract-mesh path)"
+EXTRACT_WORKLOAD = ("C3-extract: 1M synthetic Gaussians, 1920x1080, SH degree 3, no_grad render -> median-depth mask -> "
+                    "depth2point + depth2normal -> TSDF integrate (BASELINE config 3, gs-extract-mesh path)")
 CLUSTERED = {"C2-clustered": dict(cam_distance=11.0, ring=5, view=1)}
 INSIDE = {"C4-inside": dict(ball_radius=6.0, cam_radius=2.5, ring=8, sigma=0.008)}
 
@@ -183,6 +190,28 @@ def list_histogram(ranges):
             "empty_tiles": int((n == 0).sum()), "max_over_mean": round(float(n.max() / n.mean().clamp(min=1e-9)), 2)}
 
 
+DUMP_MAX_ELEMS = 1 << 20     # per array (4 MB of float32): at most 11 arrays per step, 44 MB in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor, None = absent) as dirname/<name>.npy in float32.  An array of
+    at most DUMP_MAX_ELEMS values keeps its shape; a larger one is written flat as a fixed sample: DUMP_MAX_ELEMS flat
+    indices drawn without replacement by a generator seeded with the array's name and size, in ascending order -- the same
+    elements on every run, so that two builds can be compared output for output."""
+    import zlib
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), n])
+            idx = np.sort(rng.choice(n, DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def reference_ab(sc, cam, D, grads_cpu, dev, steps=5):
     """Optional GPU A/B: the reference's OWN kernels (hipified test-only into oracle/_ref/libgsref.so by
     oracle/build_ref.sh; checker infrastructure, never part of the product) timed on the same inputs, including the
@@ -270,6 +299,7 @@ def run_extract(a, dev, scenes, _C):
     stage_names = ("render", "mask", "points", "normals", "integrate")   # fused epilogue: mask = points = 0, everything under "normals"
     acc = {k: 0.0 for k in stage_names}
     marks = []
+    last = {}                                                                   # the arrays of the latest frame (--dump-outputs)
 
     def step(i, timed=False):
         rs, Kc, E, c = rss[i % K], Ks[i % K], Es[i % K], cams[i % K]
@@ -303,6 +333,7 @@ def run_extract(a, dev, scenes, _C):
         if timed:
             e[5].record()
             marks.append(e)
+        last.update(median=median, opacity=opacity, points=pts, normals=nrm)
         return nrm, invalid
 
     for i in range(max(0, a.settle) + max(a.warmup, K)):                        # --settle (sustained clock), then the warm-up: at least one
@@ -318,6 +349,18 @@ def run_extract(a, dev, scenes, _C):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     fwd_timed = _C.last_forward_ms()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last)
+    if not a.full:
+        _C.set_profiling(False)
+        line = {"metric": EXTRACT_METRIC, "value": round(H * W * a.steps / dt / 1e6, 3), "unit": "Mpixels/s", "n_gpus": 1,
+                "steps": a.steps, "warmup": max(a.warmup, K), "settle_steps": max(0, a.settle),
+                "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic",
+                "config": {"workload": EXTRACT_WORKLOAD, "gaussians": P, "width": W, "height": H, "sh_degree": D, "cameras_cycled": K},
+                "cpu_baseline": None}
+        print(json.dumps(line), flush=True)
+        return
     _C.set_profiling(1)
     for i in range(12):
         step(a.steps + i, timed=True)
@@ -368,13 +411,12 @@ def run_extract(a, dev, scenes, _C):
                          "(GPU rasterizer; vdbfusion is an un-vendored C++ dependency)"}
     comp_ms = (fwd_ms or {}).get("composite")
     T = ((W + 15) // 16) * ((H + 15) // 16)
-    line = {"metric": "Mpixels/s depth+normal render + TSDF integrate @1M Gaussians 1920x1080 (gs-extract-mesh path)",
+    line = {"metric": EXTRACT_METRIC,
             "value": round(HW * a.steps / dt / 1e6, 3), "unit": "Mpixels/s", "n_gpus": 1, "steps": a.steps, "warmup": max(a.warmup, K),
             "settle_steps": max(0, a.settle),
             "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "C3-extract: 1M synthetic Gaussians, 1920x1080, SH degree 3, no_grad render -> median-depth mask -> "
-                                   "depth2point + depth2normal -> TSDF integrate (BASELINE config 3, gs-extract-mesh path)",
+            "config": {"workload": EXTRACT_WORKLOAD,
                        "gaussians": P, "width": W, "height": H, "sh_degree": D, "cameras_cycled": K,
                        "valid_points_per_frame": n_valid // max(1, a.steps), "tsdf": {"voxel_size": 0.04, "sdf_trunc": 0.16,
                        "hash_slots": vol.capacity, "occupied_blocks": blocks, "status": status}},
@@ -406,12 +448,12 @@ def self_launch(n):
 
 
 def other_workloads(names, steps=10, warmup=3, settle=30, exact=False, fast=False):
-    """{name: {ms_per_step, value, unit, steps, stage_ms, roofline_frac}} of `python bench.py --workload <name> --no-extras ...` run as
-    child processes (one at a time, after the headline's timed region; the parent's GPU work is finished and synchronised)."""
+    """{name: {ms_per_step, value, unit, steps, stage_ms, roofline_frac}} of `python bench.py --workload <name> --full --no-extras ...` run
+    as child processes (one at a time, after the headline's timed region; the parent's GPU work is finished and synchronised)."""
     out = {}
     for name in names:
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", str(warmup),
-               "--settle", str(settle), "--no-extras", "--no-cpu-baseline", "--no-ref-ab"] + (["--exact"] if exact else []) + (["--fast-exp"] if fast else [])
+               "--settle", str(settle), "--full", "--no-extras", "--no-cpu-baseline", "--no-ref-ab"] + (["--exact"] if exact else []) + (["--fast-exp"] if fast else [])
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         t0 = time.perf_counter()
         try:
@@ -477,6 +519,13 @@ def main():
     ap.add_argument("--traffic", type=float, default=None,
                     help="measured HBM bytes per composite_fwd launch from a rocprofv3 --pmc pass; default: the "
                          "committed measurement in profiles/r*_traffic.json for this workload, else null")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-stage times (a pass of untimed steps with stage events), "
+                         "instance counts and roofline figures, the extra blocks (rotating camera, the other compositing mode, "
+                         "colour-only loss, other workloads, the other exchange at N > 1), the CPU baseline and the reference A/B")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rendered images, radii, gradients) as "
+                         f"DIR/<name>.npy in float32; an array of more than {DUMP_MAX_ELEMS} values as a fixed, seeded sample of them")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -628,7 +677,7 @@ def main():
     settled = {"done": False}
     STAGE_STEPS = 12
 
-    def timed_run(fn, steps, warmup, timed_level=2):
+    def timed_run(fn, steps, warmup, timed_level=2, after_timed=None):
         if not settled["done"]:                              # once per process: the device at its sustained clock (see --settle)
             settled["done"] = True
             for _ in range(max(0, a.settle)):
@@ -639,8 +688,8 @@ def main():
         # The K timed steps carry HIP events around composite_fwd only (profiling level 2: two records per step on the launch
         # stream, no host synchronisation): that is the live duration `roofline` is computed from.  Events at every stage
         # boundary (nine per step) cost 3.1 % of a C3 step (1.014 against 0.983 ms, profiles/r04_warmup_ramp.txt), so the stage
-        # breakdown `stage_ms` comes from STAGE_STEPS further, untimed, steps behind the timed region; its `composite` entry is
-        # the timed steps' own.
+        # breakdown `stage_ms` comes from STAGE_STEPS further, untimed, steps behind the timed region (--full only); its
+        # `composite` entry is the timed steps' own.
         _C.set_profiling(timed_level)
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -648,12 +697,18 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         f_timed = _C.last_forward_ms()
-        _C.set_profiling(1)
-        for _ in range(STAGE_STEPS):
-            fn(False)
-        barrier()
-        f, b = _C.last_forward_ms(), _C.last_backward_ms()
-        _C.set_profiling(False)
+        if after_timed is not None:
+            after_timed()                                    # (--dump-outputs: the last timed step's results, before anything else runs)
+        if not a.full:
+            _C.set_profiling(False)
+            f = b = None
+        else:
+            _C.set_profiling(1)
+            for _ in range(STAGE_STEPS):
+                fn(False)
+            barrier()
+            f, b = _C.last_forward_ms(), _C.last_backward_ms()
+            _C.set_profiling(False)
         if f and f_timed and f_timed.get("composite"):
             f["composite_in_stage_pass"] = f["composite"]
             f["composite"] = f_timed["composite"]
@@ -705,19 +760,31 @@ def main():
                     opt_ev.append((e0, e1))
         return fn, opt_ev
 
+    def dump_last_step():
+        # what a caller of the step receives: the five outputs of the last view and the gradients of every leaf (after the
+        # exchange at N > 1); the rotating mode's optimizer update after the step changes the parameters, not these
+        if rank != 0:
+            return
+        arrays = dict(zip(("color", "radii", "depth", "median", "opacity"), state["out"]))
+        if not a.fwd_only:
+            arrays.update({f"grad_{k}": p.grad for k, p in params.items()})
+            arrays["grad_means2D"] = means2D.grad
+        dump_outputs(a.dump_outputs, arrays)
+
+    after_timed = dump_last_step if a.dump_outputs else None
     with mode:
         if rotating_headline:
             rot_fn, opt_ev = make_rotating(a.rotate_cameras)
-            dt, fwd_ms, bwd_ms = timed_run(rot_fn, a.steps, a.warmup)
+            dt, fwd_ms, bwd_ms = timed_run(rot_fn, a.steps, a.warmup, after_timed=after_timed)
             torch.cuda.synchronize()
             opt_ms = sum(x.elapsed_time(y) for x, y in opt_ev) / max(1, len(opt_ev)) if opt_ev else 0.0
             dt -= opt_ms * 1e-3 * a.steps                    # the optimizer is not part of the metric; its traffic is the point
         else:
-            dt, fwd_ms, bwd_ms = timed_run(lambda timed: step(timed), a.steps, a.warmup)
+            dt, fwd_ms, bwd_ms = timed_run(lambda timed: step(timed), a.steps, a.warmup, after_timed=after_timed)
             opt_ms = None
 
     extras = {}
-    if multi and not a.fwd_only and not a.no_extras and not rotating_headline and not state.get("fallback_reason"):
+    if a.full and multi and not a.fwd_only and not a.no_extras and not rotating_headline and not state.get("fallback_reason"):
         # N > 1: the OTHER exchange beside the headline, a few steps of the same views (north_star words the exchange as "a single
         # RCCL all-reduce": that is `dense`; the default headline is its factored form) -- both on one line.  Every rank takes
         # the same branch: `factored` / the fallback flag were agreed above.
@@ -764,7 +831,7 @@ def main():
         factored = was_factored
         del comm_ev[:]
         comm_ev.extend(head_ev)
-    if not multi and not a.no_extras and not rotating_headline and a.workload in ("C3", "C3D0"):
+    if a.full and not multi and not a.no_extras and not rotating_headline and a.workload in ("C3", "C3D0"):
         # beside the static-camera headline: (1) the rotating / optimizer-contended step (same mode), (2) the OTHER compositing mode
         K = 8
         rot_fn, opt_ev = make_rotating(K)
@@ -814,42 +881,43 @@ def main():
                         "absent -- NULL through the C ABI, no zero planes materialised (the reference reads all four, backward.cu:476-483, "
                         "and its autograd fills 41 MB of zeros per 1080p step), nothing loaded for them, composite_bwd's colour-only instantiation"}
 
-    if not multi and not a.no_extras and not rotating_headline and a.workload == "C3" and not a.fwd_only and a.loss == "all":
+    if a.full and not multi and not a.no_extras and not rotating_headline and a.workload == "C3" and not a.fwd_only and a.loss == "all":
         # the 8-GPU configurations on the driver's clock too.  One view of C4 / C4-inside / C5 each, a handful of steps
         # behind the headline, each in a child process of this very script (its own scene, its own settle steps; `--no-extras` there)
         extras["other_workloads"] = other_workloads(("C4", "C4-inside", "C5"), exact=a.exact, fast=a.fast_exp)
 
     # instance counts of this rank's view (they drive every composite-stage byte count): the reference-defined
-    # num_rendered and the instances actually binned; per-tile list lengths
-    with torch.no_grad():
-        out = _C.rasterize_gaussians(rs.bg, params["means3D"], torch.Tensor([]), params["opacities"], params["scales"],
-                                     params["rotations"], 1.0, torch.Tensor([]), rs.viewmatrix, rs.projmatrix,
-                                     rs.tanfovx, rs.tanfovy, H, W, params["shs"], D, rs.campos, False, False)
-        R_ref = out[0]
-        counts = _C.inspect_counts(out[8], W, H)
-        R = counts["num_binned"]
-        R_staged = _C.inspect_staged(out[8], W, H)            # what composite_fwd fetched before every pixel of a tile had saturated
-        _, ranges = _C.inspect_binning(out[7], out[8], R, W, H)
-        lists = list_histogram(ranges)
-        vis = int((out[5] > 0).sum().item())
-        del out
+    # num_rendered and the instances actually binned; per-tile list lengths (--full: one more forward)
+    if a.full:
+        with torch.no_grad():
+            out = _C.rasterize_gaussians(rs.bg, params["means3D"], torch.Tensor([]), params["opacities"], params["scales"],
+                                         params["rotations"], 1.0, torch.Tensor([]), rs.viewmatrix, rs.projmatrix,
+                                         rs.tanfovx, rs.tanfovy, H, W, params["shs"], D, rs.campos, False, False)
+            R_ref = out[0]
+            counts = _C.inspect_counts(out[8], W, H)
+            R = counts["num_binned"]
+            R_staged = _C.inspect_staged(out[8], W, H)        # what composite_fwd fetched before every pixel of a tile had saturated
+            _, ranges = _C.inspect_binning(out[7], out[8], R, W, H)
+            lists = list_histogram(ranges)
+            vis = int((out[5] > 0).sum().item())
+            del out
 
     if rank == 0:
         T = ((W + 15) // 16) * ((H + 15) // 16)
         ms_per_step = dt / a.steps * 1e3
         value = world * V * H * W / (dt / a.steps) / 1e6
-        comp_ms = fwd_ms["composite"] if fwd_ms else None
-        # SURVEY s8(d) bytes of composite_fwd on the instances the kernel actually STAGED (it stops fetching a tile's list, 256
-        # entries at a time, once every pixel of the tile has saturated: on dense frames -- C4: 3.4 k entries per tile, 99 % of the
-        # pixels saturated after a few hundred -- most of the binned instances are never read; dividing ALL of them by the
-        # kernel time would print a bandwidth the kernel does not have)
-        alg_bytes = R_staged * 44 + T * 8 + H * W * 32 + (0 if a.fwd_only else H * W * 8)
-        counters = committed_counters(a.workload)
+        comp_ms = fwd_ms["composite"] if fwd_ms and a.full else None
+        counters = committed_counters(a.workload) if a.full else None
         traffic = a.traffic
         if traffic is None and counters and "composite_fwd" in counters:
             traffic = counters["composite_fwd"].get("traffic_bytes")
         roof = None
         if comp_ms:
+            # SURVEY s8(d) bytes of composite_fwd on the instances the kernel actually STAGED (it stops fetching a tile's list, 256
+            # entries at a time, once every pixel of the tile has saturated: on dense frames -- C4: 3.4 k entries per tile, 99 % of the
+            # pixels saturated after a few hundred -- most of the binned instances are never read; dividing ALL of them by the
+            # kernel time would print a bandwidth the kernel does not have)
+            alg_bytes = R_staged * 44 + T * 8 + H * W * 32 + (0 if a.fwd_only else H * W * 8)
             achieved = alg_bytes / (comp_ms * 1e-3) / 1e9
             roof = {"kernel": "composite_fwd", "bound": "hbm", "achieved": round(achieved, 2), "peak": 8000.0,
                     "unit": "GB/s", "frac": round(achieved / 8000.0, 5), "traffic": traffic,
@@ -881,8 +949,7 @@ def main():
             "settle_steps": max(0, a.settle),
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "config": {"workload": desc, "gaussians": P, "visible": vis, "width": W, "height": H, "sh_degree": D,
-                       "num_rendered": R_ref, "instances_binned": R, "instances_staged_by_composite_fwd": R_staged, "tiles": T, "tile_list_length": lists,
+            "config": {"workload": desc, "gaussians": P, "width": W, "height": H, "sh_degree": D, "tiles": T,
                        "views_per_step": world * V, "views_per_rank": V,
                        "loss": "colour + depth + median + opacity gradients consumed" if a.loss == "all" else "colour gradient only (--loss color)",
                        "camera": (f"ring of {a.rotate_cameras}, a different one every step, Adam update between the steps "
@@ -892,10 +959,13 @@ def main():
                                 "profiles/r04_parity.json)") if fast_mode else
                                "bit-exact (reproducible exp: every output bit-identical to the CPU oracle; --exact / GSR_FAST_EXP=0)",
                        "parallelism": par},
-            "stage_ms": {"forward": fwd_ms, "backward": bwd_ms},
-            "stage_roofline": stage_roofline(P, vis, R, T, H, W, D, fwd_ms, bwd_ms, a.fwd_only, R_staged),
-            "roofline": roof,
         }
+        if a.full:
+            line["config"].update({"visible": vis, "num_rendered": R_ref, "instances_binned": R,
+                                   "instances_staged_by_composite_fwd": R_staged, "tile_list_length": lists})
+            line.update({"stage_ms": {"forward": fwd_ms, "backward": bwd_ms},
+                         "stage_roofline": stage_roofline(P, vis, R, T, H, W, D, fwd_ms, bwd_ms, a.fwd_only, R_staged),
+                         "roofline": roof})
         line.update(extras)
         if bwd_ms:
             line["valu_composite_bwd"] = valu_issue(counters, "composite_bwd", bwd_ms.get("composite_bwd"))
@@ -907,8 +977,8 @@ def main():
             # every dense step of the process (settle, warm-up, timed, stage pass; the `variants` block included when it ran dense)
             n_it = max(1, state.get("steps_dense", a.steps + a.warmup))
             comm = {"exchange": "factored" if factored else "dense", "exchange_fallback": state.get("fallback_reason"),
-                    "compute_ms": round(comp_total * V, 4), "comm_exposed_ms": round(exposed, 4),
-                    "note": "compute_ms = sum of the operator's kernel stages (HIP events) x views per rank; comm_exposed_ms = time "
+                    "compute_ms": round(comp_total * V, 4) if a.full else None, "comm_exposed_ms": round(exposed, 4),
+                    "note": "compute_ms = sum of the operator's kernel stages (HIP events; --full) x views per rank; comm_exposed_ms = time "
                             "from the end of the last backward's enqueue to the end of the exchange on rank 0's stream (what the "
                             "collectives add to the step after overlap)"}
             if factored:
@@ -919,11 +989,11 @@ def main():
                              "chunk_bytes_per_step": bucket.stats["chunk_bytes"] / n_it,
                              "tail_bytes_per_step": bucket.stats["tail_bytes"] / n_it})
             line["comm"] = comm
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sc, cam, D, grads_cpu)
         else:
             line["cpu_baseline"] = None
-        if world == 1 and not a.no_ref_ab and not a.fwd_only:
+        if a.full and world == 1 and not a.no_ref_ab and not a.fwd_only:
             line["reference_hipified_ms"] = reference_ab(sc, cam, D, grads_cpu, dev)
         print(json.dumps(line), flush=True)
     if multi:

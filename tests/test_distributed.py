@@ -630,7 +630,7 @@ def test_bench_py_gpus2_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(GSR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "C2", "--steps", "3", "--warmup", "1",
-                        "--settle", "0", "--no-cpu-baseline", "--no-ref-ab"], env=env, capture_output=True, text=True, timeout=600)
+                        "--settle", "0", "--full", "--no-cpu-baseline", "--no-ref-ab"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

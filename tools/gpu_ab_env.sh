@@ -4,7 +4,7 @@ name="$1"; var="$2"; vals="$3"; wls="$4"; kexpr="${5:-none}"
 out="gpurun_out/$name"; mkdir -p "$out"; export HSA_ENABLE_IPC_MODE_LEGACY=0
 if [ "$kexpr" != "none" ]; then timeout 1200 python -m pytest tests -m gpu -q -x -p no:cacheprovider -k "$kexpr" 2>&1 | tail -3; fi
 for rep in 1 2; do for v in $vals; do for w in $wls; do
-  env $var=$v timeout 300 python bench.py --workload $w --steps 40 --warmup 10 --no-cpu-baseline --no-ref-ab --no-extras > "$out/${var}${v}_${w}_$rep.json" 2> "$out/${var}${v}_${w}_$rep.err"
+  env $var=$v timeout 300 python bench.py --full --workload $w --steps 40 --warmup 10 --no-cpu-baseline --no-ref-ab --no-extras > "$out/${var}${v}_${w}_$rep.json" 2> "$out/${var}${v}_${w}_$rep.err"
   python - "$out/${var}${v}_${w}_$rep.json" "$var=$v" "$w" <<'PY'
 import json, sys
 try:

@@ -11,7 +11,7 @@ for v in $variants; do
   tag="${v%%:*}"; envs="${v#*:}"
   for w in ${GSR_QUICK_WORKLOADS:-C3 C4}; do
     ( IFS=','; for e in $envs; do [ -n "$e" ] && export "$e"; done
-      timeout 300 python bench.py --workload $w --steps 30 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_${w}_$tag.json" 2> "$out/bench_${w}_$tag.err" )
+      timeout 300 python bench.py --full --workload $w --steps 30 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_${w}_$tag.json" 2> "$out/bench_${w}_$tag.err" )
     python - "$out/bench_${w}_$tag.json" "$tag" <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ if [ "$kexpr" != "none" ]; then
   timeout 1500 python -m pytest tests -m gpu -q -x -p no:cacheprovider -k "$kexpr" > "$out/pytest.log" 2>&1; echo "pytest rc=$?" | tee "$out/summary.txt"; tail -6 "$out/pytest.log" | cut -c1-300 | tee -a "$out/summary.txt"
 fi
 for w in $wls; do
-  timeout 300 python bench.py --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab --no-extras $extra > "$out/bench_$w.json" 2> "$out/bench_$w.err"
+  timeout 300 python bench.py --full --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab --no-extras $extra > "$out/bench_$w.json" 2> "$out/bench_$w.err"
 done
 python - "$out" <<'PY' | tee -a "$out/summary.txt"
 import json, sys, glob, os

@@ -14,11 +14,11 @@ if [ "$what" = "tests" ] || [ "$what" = "all" ]; then
 fi
 if [ "$what" = "bench" ] || [ "$what" = "all" ]; then
   echo "== bench" | tee -a "$out/summary.txt"
-  timeout 600 python bench.py > "$out/bench_c3.json" 2> "$out/bench_c3.err"; echo "bench C3 rc=$?" | tee -a "$out/summary.txt"
+  timeout 600 python bench.py --full > "$out/bench_c3.json" 2> "$out/bench_c3.err"; echo "bench C3 rc=$?" | tee -a "$out/summary.txt"
   for w in C3D0 C2 C4 C5; do
-    timeout 300 python bench.py --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_$w.json" 2> "$out/bench_$w.err"; echo "bench $w rc=$?" | tee -a "$out/summary.txt"
+    timeout 300 python bench.py --full --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_$w.json" 2> "$out/bench_$w.err"; echo "bench $w rc=$?" | tee -a "$out/summary.txt"
   done
-  timeout 300 python bench.py --fwd-only --steps 30 --warmup 10 --no-cpu-baseline > "$out/bench_c3_fwd.json" 2> "$out/bench_c3_fwd.err"
+  timeout 300 python bench.py --full --fwd-only --steps 30 --warmup 10 --no-cpu-baseline > "$out/bench_c3_fwd.json" 2> "$out/bench_c3_fwd.err"
   python - "$out" <<'PY' | tee -a "$out/summary.txt"
 import json, sys, glob, os
 for f in sorted(glob.glob(os.path.join(sys.argv[1], "bench_*.json"))):

@@ -13,12 +13,12 @@ if [ "$what" = "tests" ] || [ "$what" = "all" ]; then
 fi
 if [ "$what" = "bench" ] || [ "$what" = "all" ]; then
   echo "== bench" | tee -a "$out/summary.txt"
-  timeout 600 python bench.py > "$out/bench_c3.json" 2> "$out/bench_c3.err"; echo "bench C3 rc=$?" | tee -a "$out/summary.txt"
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-extras > "$out/bench_c3_driver_flags.json" 2> "$out/bench_c3_driver_flags.err"
+  timeout 600 python bench.py --full > "$out/bench_c3.json" 2> "$out/bench_c3.err"; echo "bench C3 rc=$?" | tee -a "$out/summary.txt"
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-extras > "$out/bench_c3_driver_flags.json" 2> "$out/bench_c3_driver_flags.err"
   for w in C4 C4-inside C5 C2-clustered C3D0; do
-    timeout 300 python bench.py --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_$w.json" 2> "$out/bench_$w.err"; echo "bench $w rc=$?" | tee -a "$out/summary.txt"
+    timeout 300 python bench.py --full --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_$w.json" 2> "$out/bench_$w.err"; echo "bench $w rc=$?" | tee -a "$out/summary.txt"
   done
-  timeout 300 python bench.py --workload C4-inside --loss color --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_C4-inside_color.json" 2> "$out/bench_C4-inside_color.err"
+  timeout 300 python bench.py --full --workload C4-inside --loss color --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_C4-inside_color.json" 2> "$out/bench_C4-inside_color.err"
   python - "$out" <<'PY' | tee -a "$out/summary.txt"
 import json, sys, glob, os
 r4 = lambda d: {k: round(v, 4) for k, v in (d or {}).items() if isinstance(v, float)}

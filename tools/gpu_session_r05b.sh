@@ -7,14 +7,14 @@ timeout 900 python -m pytest tests -m gpu -q -x -p no:cacheprovider -k "gating o
 B="--steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab --no-extras"
 for w in C4-inside C4 C3; do
   for g in 0 1; do
-    GSR_SH_PREFETCH=$g timeout 300 python bench.py --workload $w $B > "$out/bench_${w}_gate$g.json" 2> "$out/bench_${w}_gate$g.err"
+    GSR_SH_PREFETCH=$g timeout 300 python bench.py --full --workload $w $B > "$out/bench_${w}_gate$g.json" 2> "$out/bench_${w}_gate$g.err"
   done
 done
 # the N > 1 code path on one GPU (process group of one rank over RCCL): per-rank compute of the factored / dense step
 for w in C3 C4 C4-inside; do
   for ex in "factored none" "factored view" "dense none"; do
     set -- $ex
-    GSR_BENCH_FORCE_PG=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 300 python bench.py --gpus 1 --workload $w $B --exchange $1 --compact $2 > "$out/pg1_${w}_$1_$2.json" 2> "$out/pg1_${w}_$1_$2.err"
+    GSR_BENCH_FORCE_PG=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 300 python bench.py --full --gpus 1 --workload $w $B --exchange $1 --compact $2 > "$out/pg1_${w}_$1_$2.json" 2> "$out/pg1_${w}_$1_$2.err"
   done
 done
 python - "$out" <<'PY' | tee -a "$out/summary.txt"

@@ -23,13 +23,13 @@ if [ "$what" = "tests" ] || [ "$what" = "all" ]; then
 fi
 if [ "$what" = "bench" ] || [ "$what" = "all" ]; then
   echo "== bench" | tee -a "$out/summary.txt"
-  timeout 900 python bench.py > "$out/bench_c3.json" 2> "$out/bench_c3.err"; echo "bench C3 (default command) rc=$?" | tee -a "$out/summary.txt"
-  timeout 600 python bench.py --steps 20 --warmup 5 > "$out/bench_c3_driver_flags.json" 2> "$out/bench_c3_driver_flags.err"
+  timeout 900 python bench.py --full > "$out/bench_c3.json" 2> "$out/bench_c3.err"; echo "bench C3 (default command) rc=$?" | tee -a "$out/summary.txt"
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > "$out/bench_c3_driver_flags.json" 2> "$out/bench_c3_driver_flags.err"
   for w in C4 C4-inside C5 C2-clustered C3D0 C2 C1; do
-    timeout 300 python bench.py --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_$w.json" 2> "$out/bench_$w.err"; echo "bench $w rc=$?" | tee -a "$out/summary.txt"
+    timeout 300 python bench.py --full --workload $w --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_$w.json" 2> "$out/bench_$w.err"; echo "bench $w rc=$?" | tee -a "$out/summary.txt"
   done
-  timeout 300 python bench.py --workload C3-extract --steps 20 --warmup 5 > "$out/bench_C3-extract.json" 2> "$out/bench_C3-extract.err"
-  timeout 300 python bench.py --workload C4-inside --loss color --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_C4-inside_color.json" 2> "$out/bench_C4-inside_color.err"
+  timeout 300 python bench.py --full --workload C3-extract --steps 20 --warmup 5 > "$out/bench_C3-extract.json" 2> "$out/bench_C3-extract.err"
+  timeout 300 python bench.py --full --workload C4-inside --loss color --steps 20 --warmup 10 --no-cpu-baseline --no-ref-ab > "$out/bench_C4-inside_color.json" 2> "$out/bench_C4-inside_color.err"
   python - "$out" <<'PY' | tee -a "$out/summary.txt"
 import json, sys, glob, os
 r4 = lambda d: {k: round(v, 4) for k, v in (d or {}).items() if isinstance(v, float)}
@@ -47,9 +47,9 @@ fi
 if [ "$what" = "dc" ] || [ "$what" = "all" ]; then
   # rocprofv3 kernel stats of the DEFAULT command's timed loop (settle + warm-up + timed + stage steps at warm clocks): its average
   # for composite_fwd must agree with the live HIP-event figure of the same run (`roofline.avg_ms`)
-  echo "== rocprofv3 --kernel-trace --stats -- python bench.py --no-extras" | tee -a "$out/summary.txt"
+  echo "== rocprofv3 --kernel-trace --stats -- python bench.py --full --no-extras" | tee -a "$out/summary.txt"
   root="$(pwd)"
-  ( cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$root/$out/dc" -o k -- python "$root/bench.py" --no-extras --no-cpu-baseline --no-ref-ab > "$root/$out/dc.log" 2>&1 )
+  ( tmp="$(mktemp -d)" && cd "$tmp" && export TMPDIR="$tmp" && timeout 900 rocprofv3 --kernel-trace --stats -d "$root/$out/dc" -o k -- python "$root/bench.py" --full --no-extras --no-cpu-baseline --no-ref-ab > "$root/$out/dc.log" 2>&1 )
   grep '^{"metric"' "$out/dc.log" | tail -1 > "$out/c3_default_command_bench_line.json"
   db=$(ls "$out"/dc/*/k_results.db "$out"/dc/k_results.db 2>/dev/null | head -1)
   python tools/rocpd_summary.py "$db" > "$out/c3_default_command_kernel_stats.txt" 2>&1

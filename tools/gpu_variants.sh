@@ -11,7 +11,7 @@ for rep in 1 2; do
 for tag in $tags; do
   cp "gpurun_variants/libgsrast_$tag.so" gaustudio_amd/libgsrast.so
   for w in $wls; do
-    timeout 300 python bench.py --workload $w --steps 40 --warmup 10 --no-cpu-baseline --no-ref-ab --no-extras $extra > "$out/${tag}_${w}_$rep.json" 2> "$out/${tag}_${w}_$rep.err"
+    timeout 300 python bench.py --full --workload $w --steps 40 --warmup 10 --no-cpu-baseline --no-ref-ab --no-extras $extra > "$out/${tag}_${w}_$rep.json" 2> "$out/${tag}_${w}_$rep.err"
     python - "$out/${tag}_${w}_$rep.json" "$tag" "$w" <<'PY'
 import json, sys
 try:

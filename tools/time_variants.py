@@ -4,7 +4,7 @@
     python tools/time_variants.py --variants base,coop --workloads C3,C4 --reps 2 --keys forward.preprocess,backward.composite_bwd
 
 For every variant: gpurun_variants/libgsrast_<name>.so is copied over gaustudio_amd/libgsrast.so (the original is restored at the
-end), then `python bench.py --workload W --steps S --warmup 10 --no-extras --no-cpu-baseline --no-ref-ab` runs `reps` times per
+end), then `python bench.py --workload W --steps S --warmup 10 --full --no-extras --no-cpu-baseline --no-ref-ab` runs `reps` times per
 workload, interleaved across the variants so that clock drift hits them alike.  Prints one table row per (workload, variant):
 ms_per_step and the requested stage_ms entries, every repetition."""
 import argparse
@@ -38,7 +38,7 @@ def main():
                 for v in variants:
                     shutil.copy2(os.path.join(ROOT, "gpurun_variants", f"libgsrast_{v}.so"), LIB)
                     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--steps", str(a.steps), "--warmup", "10",
-                           "--no-extras", "--no-cpu-baseline", "--no-ref-ab"] + a.extra.split()
+                           "--full", "--no-extras", "--no-cpu-baseline", "--no-ref-ab"] + a.extra.split()
                     r = subprocess.run(cmd, capture_output=True, text=True)
                     rows = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
                     if r.returncode != 0 or not rows:

@@ -1264,4 +1264,183 @@ int gsr_inspect_image(const char* image_buffer, int width, int height, float* fi
 	return GSR_OK;
 }
 
+// ---- 2D Gaussian surfels (gsr_surfel.hip; include/gsrast.h) ----
+// The forward reads the instance count back before it sizes the binning buffer (no speculative launch: a plain count read-back,
+// the reference's own order), then runs the 3DGS binning, scan and sort launchers unchanged on the surfels' 16-B binning records.
+int gsr_surfel_forward(const gsr_options* opt, gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn binning_alloc,
+                       void* binning_ctx, gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
+                       int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                       const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                       const float* viewmatrix, const float* projmatrix, const float* cam_pos, float* out_color, float* out_allmap,
+                       int* radii, int debug, void* stream)
+{
+	hipStream_t s = (hipStream_t)stream;
+	g_err.clear();
+	if (width <= 0 || height <= 0) return fail(GSR_ERR_ARG, "gsr_surfel_forward: bad image size", __FILE__, __LINE__);
+	if (!out_color || !out_allmap) return fail(GSR_ERR_ARG, "gsr_surfel_forward: NULL output", __FILE__, __LINE__);
+	if (!geometry_alloc || !binning_alloc || !image_alloc)
+		return fail(GSR_ERR_ARG, "gsr_surfel_forward: NULL allocator", __FILE__, __LINE__);
+	const size_t HW = (size_t)width * height;
+	if (P <= 0) {
+		HIP_TRY(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * HW, s));
+		HIP_TRY(hipMemsetAsync(out_allmap, 0, sizeof(float) * 7 * HW, s));
+		return 0;
+	}
+	if (!means3D || !opacities || !scales || !rotations || !viewmatrix || !projmatrix || !cam_pos || !radii)
+		return fail(GSR_ERR_ARG, "gsr_surfel_forward: NULL required input", __FILE__, __LINE__);
+	if ((colors_precomp != nullptr) == (shs != nullptr))
+		return fail(GSR_ERR_ARG, "gsr_surfel_forward: provide exactly one of SHs or precomputed colours", __FILE__, __LINE__);
+	if (!colors_precomp && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
+		return fail(GSR_ERR_ARG, "gsr_surfel_forward: SH degree does not fit the stored coefficients", __FILE__, __LINE__);
+	{
+		const int rc = check_sticky("gsr_surfel_forward");
+		if (rc < 0) return rc;
+	}
+	const Resolved ro = resolve_options(opt);
+	const SurfGeomLayout gl((size_t)P);
+	const ImgLayout il0(width, height);
+	if (!bin_lds_path_ok(il0.T))
+		return fail(GSR_ERR_ARG, "gsr_surfel_forward: image too large (the surfel path bins through the LDS tile histogram only)", __FILE__, __LINE__);
+	const SurfImgLayout sl(width, height, bin_hist_bytes(P, il0.T));
+	const ImgLayout& il = sl.il;
+	char* geom = geometry_alloc(geometry_ctx, gl.total);
+	char* img = image_alloc(image_ctx, sl.total);
+	if (!geom || !img) return fail(GSR_ERR_ALLOC, "gsr_surfel_forward: allocator returned NULL", __FILE__, __LINE__);
+	remember_forward_mode(img, ro.fast_exp != 0, 0);
+
+	GsCam* cam = reinterpret_cast<GsCam*>(geom + gl.cam);
+	SurfRec* recs = reinterpret_cast<SurfRec*>(geom + gl.recs);
+	uint32_t* tiles_touched = reinterpret_cast<uint32_t*>(geom + gl.tiles_touched);
+	uint32_t* goff = reinterpret_cast<uint32_t*>(geom + gl.goff);
+	uint32_t* bsums = reinterpret_cast<uint32_t*>(geom + gl.bsums);
+	uint32_t* refsums = reinterpret_cast<uint32_t*>(geom + gl.refsums);
+	uint4* binfo = reinterpret_cast<uint4*>(geom + gl.binfo);
+	GsCtl* ctl = reinterpret_cast<GsCtl*>(img + il.ctl);
+	uint2* ranges = reinterpret_cast<uint2*>(img + il.ranges);
+	uint32_t* tile_count = reinterpret_cast<uint32_t*>(img + il.tile_count);
+	uint32_t* Hm = reinterpret_cast<uint32_t*>(img + sl.hist);
+	{
+		const float* const src[4] = {viewmatrix, projmatrix, cam_pos, background};
+		float* const dst[4] = {cam->view, cam->proj, cam->campos, cam->bg};
+		const int n[4] = {16, 16, 3, 3};
+		HIP_TRY(stage_small(src, dst, n, s, &ctl->opts, ro.fast_exp ? GSR_CTL_OPT_FAST_EXP : 0u, reinterpret_cast<uint32_t*>(ctl), 8));
+	}
+	SurfFwdArgs a;
+	a.P = P; a.D = D; a.M = M; a.W = width; a.H = height;
+	a.means3D = means3D; a.shs = shs; a.colors_precomp = colors_precomp; a.opacities = opacities;
+	a.scales = scales; a.scale_modifier = scale_modifier; a.rotations = rotations;
+	launch_surfel_preprocess_fwd(a, cam, il, radii, recs, reinterpret_cast<float*>(geom + gl.shjac), binfo, tiles_touched, bsums, refsums, s);
+	STAGE_CHECK("surfel_preprocess_fwd", debug, s);
+	launch_bin_hist(P, il.gx, il.T, tiles_touched, nullptr, binfo, Hm, tile_count, s);
+	STAGE_CHECK("bin_hist", debug, s);
+	GsCtl* host = pinned_ctl();
+	if (!host) return fail(GSR_ERR_HIP, "hipHostMalloc", __FILE__, __LINE__);
+	launch_tile_scan(il.T, tile_count, ranges, (int)gl.nblk, bsums, refsums, ctl, host, s);
+	STAGE_CHECK("tile_scan", debug, s);
+	hipEvent_t ev = readback_event();
+	if (ev) {
+		HIP_TRY(hipEventRecord(ev, s));
+		HIP_TRY(hipEventSynchronize(ev));
+	} else
+		HIP_TRY(hipStreamSynchronize(s));
+	const uint32_t R = host->num_binned, max_tile = host->max_tile_count;
+	if ((host->err_overflow & 1u) || host->ref_rendered > 0x7fffffffu || R > 0x7fffffffu)
+		return fail(GSR_ERR_ARG, "gsr_surfel_forward: more than 2^31 - 1 (tile, surfel) instances", __FILE__, __LINE__);
+	const int long_level = max_tile > GSR_SORT_GIANT ? 2 : (max_tile > GSR_SORT_LDS_MAX ? 1 : 0);
+	const BinLayout bl((size_t)R, long_level > 0, il.T);
+	char* bin = binning_alloc(binning_ctx, bl.total);
+	if (!bin) return fail(GSR_ERR_ALLOC, "gsr_surfel_forward: binning allocator returned NULL", __FILE__, __LINE__);
+	uint64_t* keys = reinterpret_cast<uint64_t*>(bin + bl.keys);
+	uint64_t* keys2 = reinterpret_cast<uint64_t*>(bin + bl.keys2);
+	uint32_t* point_list = reinterpret_cast<uint32_t*>(bin + bl.point_list);
+	if (R > 0) {
+		launch_bin_scatter2(P, il.gx, il.T, tiles_touched, nullptr, binfo, Hm, ranges, keys, bsums, goff, ctl, R, s);   // (+ goff)
+		STAGE_CHECK("bin_scatter", debug, s);
+		launch_tile_sort(il.T, true, long_level, ranges, keys, keys2, point_list, bin + bl.queue, (size_t)R, ctl, R,
+		                 long_level > 0 ? sticky_word() : nullptr, s);
+		STAGE_CHECK("tile_sort", debug, s);
+	} else {
+		launch_goff_apply(P, tiles_touched, bsums, goff, s);
+		STAGE_CHECK("goff_apply", debug, s);
+	}
+	launch_surfel_composite_fwd(il, width, height, ranges, point_list, recs, cam, out_color, out_allmap,
+	                            reinterpret_cast<float*>(img + il.final_T), reinterpret_cast<uint32_t*>(img + il.n_contrib),
+	                            reinterpret_cast<uint32_t*>(img + il.med_pos), reinterpret_cast<float*>(img + sl.m1),
+	                            reinterpret_cast<float*>(img + sl.m2), reinterpret_cast<float*>(img + sl.m0), ro.fast_exp != 0, s);
+	STAGE_CHECK("surfel_composite_fwd", debug, s);
+	return (int)R;
+}
+
+size_t gsr_surfel_scratch_bytes(int P, int R)
+{
+	(void)P;
+	return align_up(sizeof(float) * GSR_SURF_ROW * (size_t)(R > 0 ? R : 1));
+}
+
+int gsr_surfel_backward(const gsr_options* opt, int P, int D, int M, int R, int width, int height, const float* means3D,
+                        const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                        const float* rotations, const int* radii, const char* geom_buffer, const char* binning_buffer,
+                        const char* image_buffer, const float* out_color, const float* out_allmap, const float* dL_dout_color,
+                        const float* dL_dout_allmap, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                        float* dL_dsh, float* dL_dscale, float* dL_drot, char* scratch, int debug, void* stream)
+{
+	hipStream_t s = (hipStream_t)stream;
+	g_err.clear();
+	if (P <= 0) return GSR_OK;
+	if (!geom_buffer || !image_buffer || !binning_buffer || !scratch || !radii || !means3D || !scales || !rotations || !out_color || !out_allmap)
+		return fail(GSR_ERR_ARG, "gsr_surfel_backward: NULL input", __FILE__, __LINE__);
+	if (!dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D || !dL_dscale || !dL_drot || (shs && !dL_dsh))
+		return fail(GSR_ERR_ARG, "gsr_surfel_backward: NULL output", __FILE__, __LINE__);
+	if (shs && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
+		return fail(GSR_ERR_ARG, "gsr_surfel_backward: SH degree does not fit the stored coefficients", __FILE__, __LINE__);
+	const SurfGeomLayout gl((size_t)P);
+	const ImgLayout il0(width, height);
+	const SurfImgLayout sl(width, height, bin_hist_bytes(P, il0.T));
+	const ImgLayout& il = sl.il;
+	const BinLayout bl((size_t)(R > 0 ? R : 0));
+	FwdMode fwd;
+	{
+		const int rc = lookup_forward(image_buffer, il.ctl, s, &fwd);
+		if (rc < 0) return rc;
+	}
+	Resolved ro = resolve_options(opt);
+	if (!ro.fast_exp_explicit) ro.fast_exp = fwd.fast_exp;
+	if ((ro.fast_exp != 0) != (fwd.fast_exp != 0))
+		return fail(GSR_ERR_ARG, "gsr_surfel_backward: fast_exp differs from the forward that produced these buffers", __FILE__, __LINE__);
+	const GsCam* cam = reinterpret_cast<const GsCam*>(geom_buffer + gl.cam);
+	const SurfRec* recs = reinterpret_cast<const SurfRec*>(geom_buffer + gl.recs);
+	const uint32_t* goff = reinterpret_cast<const uint32_t*>(geom_buffer + gl.goff);
+	const uint4* binfo = reinterpret_cast<const uint4*>(geom_buffer + gl.binfo);
+	float* rows = reinterpret_cast<float*>(scratch);
+	if (R > 0) {
+		// rows of list entries behind every pixel's last contributor are not written by the walk: zero
+		HIP_TRY(hipMemsetAsync(rows, 0, sizeof(float) * GSR_SURF_ROW * (size_t)R, s));
+		launch_surfel_composite_bwd(il, width, height, reinterpret_cast<const uint2*>(image_buffer + il.ranges),
+		                            reinterpret_cast<const uint32_t*>(binning_buffer + bl.point_list), recs, binfo, goff,
+		                            reinterpret_cast<const float*>(image_buffer + il.final_T),
+		                            reinterpret_cast<const uint32_t*>(image_buffer + il.n_contrib),
+		                            reinterpret_cast<const uint32_t*>(image_buffer + il.med_pos),
+		                            reinterpret_cast<const float*>(image_buffer + sl.m1), reinterpret_cast<const float*>(image_buffer + sl.m2),
+		                            reinterpret_cast<const float*>(image_buffer + sl.m0), out_color, out_allmap, dL_dout_color, dL_dout_allmap, rows, ro.fast_exp != 0, s);
+		STAGE_CHECK("surfel_composite_bwd", debug, s);
+	}
+	launch_surfel_preprocess_bwd(P, width, height, means3D, scales, scale_modifier, rotations, radii, cam, recs, goff, rows, dL_dmean2D,
+	                             dL_dopacity, dL_dcolor, dL_dmean3D, dL_dscale, dL_drot, s);
+	STAGE_CHECK("surfel_preprocess_bwd", debug, s);
+	if (shs) {
+		// the SH stage of the 3DGS backward, unchanged: dL_dcolor (clamp-masked by the binning record's clamp bits) -> dL_dsh,
+		// plus the view-direction term added into dL_dmean3D
+		BwdArgs a;
+		a.P = P; a.D = D; a.M = M; a.W = width; a.H = height;
+		a.means3D = means3D; a.shs = shs; a.colors_precomp = nullptr; a.scales = nullptr; a.scale_modifier = scale_modifier;
+		a.rotations = nullptr; a.cov3D_precomp = nullptr; a.tan_fovx = 1.f; a.tan_fovy = 1.f; a.radii = radii;
+		a.shs_rest = nullptr; a.act = 0;
+		const uint32_t* clampw = reinterpret_cast<const uint32_t*>(geom_buffer + gl.binfo) + 2;
+		launch_preprocess_bwd(a, cam, nullptr, clampw, reinterpret_cast<const float*>(geom_buffer + gl.shjac), goff, rows, nullptr,
+		                      dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, nullptr, dL_dsh, nullptr, dL_dscale, dL_drot, GSR_PART_SH, 0, P, s);
+		STAGE_CHECK("preprocess_bwd_sh", debug, s);
+	}
+	return GSR_OK;
+}
+
 }  // extern "C"

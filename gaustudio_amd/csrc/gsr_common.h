@@ -636,3 +636,59 @@ __device__ __forceinline__ bool gs_msg_lookup(const uint32_t* __restrict__ msg, 
 	row = r + (uint32_t)__popc(word & ((1u << (idx & 31)) - 1u));
 	return true;
 }
+
+// ---- 2D Gaussian surfels (gsr_surfel.hip): the compatibility contract of diff_surfel_rasterization ----
+// The constants of the public 2DGS kernels, in one place; tests/surfel_model.py restates them.
+#define GSR_SURF_NEAR 0.2f            // near plane: cull at view z <= NEAR, skip a pixel whose ray depth is < NEAR
+#define GSR_SURF_FAR 100.0f           // far plane of the distortion's normalised depth m = FAR / (FAR - NEAR) * (1 - NEAR / z)
+#define GSR_SURF_LOWPASS 2.0f         // rho2 = LOWPASS * |centre - pixel|^2 (the screen-space low-pass filter, 0.707^2 = 1/2)
+#define GSR_SURF_CUTOFF 3.0f          // 3 sigma: f = (CUTOFF^2, CUTOFF^2, -1) in the centre / extent of the splat
+#define GSR_SURF_MIN_EXTENT (3.0f * 0.707106f)   // lower bound of the radius before ceil
+#define GSR_SURF_ALPHA_MAX 0.99f
+#define GSR_SURF_ALPHA_MIN (1.0f / 255.0f)
+#define GSR_SURF_T_MIN 0.0001f        // stop before T (1 - alpha) drops below this
+#define GSR_SURF_MEDIAN_T 0.5f        // median depth: the depth of the last contributor entered with T > MEDIAN_T
+
+// SH -> RGB for a unit view direction (x, y, z): rgb = max(0, sum_k basis_k sh_k + 0.5), returns the clamp mask (bit ch:
+// channel ch was clamped).  A COPY of gs_sh_to_rgb in gsr_kernels_fwd.hip (computeColorFromSH, forward.cu:20-71), operation for
+// operation, with the constant tables passed in (each translation unit keeps its own __constant__ copies); used by the surfel
+// preprocess.  The 3DGS preprocess keeps its own copy so that its code is unchanged: the two must be kept in step.
+template <int D>
+__device__ __forceinline__ uint32_t gs_sh_eval(const float C0, const float C1, const float* __restrict__ C2, const float* __restrict__ C3,
+                                               const float* sh, const float x, const float y, const float z, float* rgb)
+{
+	uint32_t clamped = 0;
+#pragma unroll
+	for (int ch = 0; ch < 3; ch++) {
+#define SH(k) sh[(k) * 3 + ch]
+		float r = C0 * SH(0);
+		if (D > 0) {
+			r = FMA(-(C1 * y), SH(1), r);
+			r = FMA(C1 * z, SH(2), r);
+			r = FMA(-(C1 * x), SH(3), r);
+			if (D > 1) {
+				const float xx = x * x, yy = y * y, zz = z * z;
+				const float xy = x * y, yz = y * z, xz = x * z;
+				r = FMA(C2[0] * xy, SH(4), r);
+				r = FMA(C2[1] * yz, SH(5), r);
+				r = FMA(C2[2] * (FMA(2.0f, zz, -xx) - yy), SH(6), r);
+				r = FMA(C2[3] * xz, SH(7), r);
+				r = FMA(C2[4] * (xx - yy), SH(8), r);
+				if (D > 2) {
+					r = FMA(C3[0] * y * FMA(3.0f, xx, -yy), SH(9), r);
+					r = FMA(C3[1] * xy * z, SH(10), r);
+					r = FMA(C3[2] * y * (FMA(4.0f, zz, -xx) - yy), SH(11), r);
+					r = FMA(C3[3] * z * FMA(-3.0f, yy, FMA(-3.0f, xx, 2.0f * zz)), SH(12), r);
+					r = FMA(C3[4] * x * (FMA(4.0f, zz, -xx) - yy), SH(13), r);
+					r = FMA(C3[5] * z * (xx - yy), SH(14), r);
+					r = FMA(C3[6] * x * FMA(-3.0f, yy, xx), SH(15), r);
+				}
+			}
+		}
+#undef SH
+		r += 0.5f;
+		if (r < 0) clamped |= 1u << ch;
+		rgb[ch] = fmaxf(r, 0.0f);
+	}
+	return clamped;
+}

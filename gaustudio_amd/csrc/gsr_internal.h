@@ -224,4 +224,76 @@ void launch_inspect_sums(int P, const int* radii, const GsRec* recs, const uint3
                          const uint8_t* row_flags,
                          float* sums10, hipStream_t s);
 
+// --- 2D Gaussian surfels (gsr_surfel.hip) ---
+// Per-surfel record, 80 B: the splat-to-pixel matrix M (rows Tu, Tv, Tw: pixel-homogeneous h = M (u, v, 1)), the screen
+// centre, opacity, the camera-facing view-space normal, RGB, the view depth (sort key) and the sign the normal was flipped by.
+//   q0 = {Tu.x, Tu.y, Tu.z, Tv.x}   q1 = {Tv.y, Tv.z, Tw.x, Tw.y}   q2 = {Tw.z, centre.x, centre.y, opacity}
+//   q3 = {n.x, n.y, n.z, radius}    q4 = {r, g, b, 0}  (q4.w: the normal's flip sign, +-1)
+struct __attribute__((aligned(16))) SurfRec {
+	float4 q0, q1, q2, q3, q4;
+};
+static_assert(sizeof(SurfRec) == 80, "SurfRec must be 80 bytes");
+// geometry buffer of a surfel forward: the 3DGS layout (GeomLayout) with 80-B records in place of the 64-B ones; the
+// camera block, tiles_touched, goff, the block sums, shjac and the 16-B binning records keep their formats, so that the
+// binning, scan, sort and SH-backward launchers run on it unchanged
+struct SurfGeomLayout {
+	size_t cam, recs, tiles_touched, goff, bsums, refsums, shjac, binfo, total;
+	size_t nblk;
+	explicit SurfGeomLayout(size_t P)
+	{
+		nblk = (P + GSR_PRE_BLOCK - 1) / GSR_PRE_BLOCK;
+		cam = 0;
+		recs = align_up(sizeof(GsCam));
+		tiles_touched = recs + align_up(sizeof(SurfRec) * P);
+		goff = tiles_touched + align_up(sizeof(uint32_t) * P);
+		bsums = goff + align_up(sizeof(uint32_t) * (P + 1));
+		refsums = bsums + align_up(sizeof(uint32_t) * (nblk + 1));
+		shjac = refsums + align_up(sizeof(uint32_t) * (nblk + 1));
+		binfo = shjac + align_up(sizeof(float) * 9 * P);
+		total = binfo + align_up(sizeof(uint4) * P);
+	}
+};
+// image buffer of a surfel forward: the 3DGS ImgLayout (ctl, ranges, tile counts, final T, contributor count, median position)
+// followed by the final M1 = sum w (m - mref), M2 = sum w (m - mref)^2 and mref (m of the pixel's first contributor) of every
+// pixel (tile-major like final_T), then the binning histogram
+struct SurfImgLayout {
+	ImgLayout il;
+	size_t m1, m2, m0, hist, total;
+	SurfImgLayout(int W, int H, size_t hist_bytes) : il(W, H)
+	{
+		m1 = il.total;
+		m2 = m1 + align_up(sizeof(float) * (size_t)il.T * GSR_TILE_PIX);
+		m0 = m2 + align_up(sizeof(float) * (size_t)il.T * GSR_TILE_PIX);
+		hist = m0 + align_up(sizeof(float) * (size_t)il.T * GSR_TILE_PIX);
+		total = hist + align_up(hist_bytes > 0 ? hist_bytes : 1);
+	}
+};
+// one row of partial sums per (tile, surfel) instance, Gaussian-major (row = goff[g] + raster index of the tile in the rect):
+//   0..8 dL/dM (Tu, Tv, Tw) | 9 dL/dopacity | 10..12 dL/dRGB | 13..15 dL/dnormal
+#define GSR_SURF_ROW 16
+struct SurfFwdArgs {
+	int P, D, M, W, H;
+	const float* means3D;
+	const float* shs;
+	const float* colors_precomp;
+	const float* opacities;
+	const float* scales;      // [P, 2]
+	float scale_modifier;
+	const float* rotations;   // [P, 4], normalised in the kernel
+};
+void launch_surfel_preprocess_fwd(const SurfFwdArgs& a, const GsCam* cam, const ImgLayout& il, int* radii, SurfRec* recs, float* shjac,
+                                  uint4* binfo, uint32_t* tiles_touched, uint32_t* bsums, uint32_t* refsums, hipStream_t s);
+void launch_surfel_composite_fwd(const ImgLayout& il, int W, int H, const uint2* ranges, const uint32_t* point_list, const SurfRec* recs,
+                                 const GsCam* cam, float* out_color, float* out_allmap, float* final_T, uint32_t* n_contrib,
+                                 uint32_t* med_pos, float* m1, float* m2, float* m0, bool fast_exp, hipStream_t s);
+void launch_surfel_composite_bwd(const ImgLayout& il, int W, int H, const uint2* ranges, const uint32_t* point_list, const SurfRec* recs,
+                                 const uint4* binfo, const uint32_t* goff, const float* final_T,
+                                 const uint32_t* n_contrib, const uint32_t* med_pos, const float* m1, const float* m2, const float* m0,
+                                 const float* out_color, const float* out_allmap, const float* dL_dcolor, const float* dL_dallmap,
+                                 float* rows, bool fast_exp, hipStream_t s);
+void launch_surfel_preprocess_bwd(int P, int W, int H, const float* means3D, const float* scales, float scale_modifier,
+                                  const float* rotations, const int* radii, const GsCam* cam, const SurfRec* recs,
+                                  const uint32_t* goff, const float* rows, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor,
+                                  float* dL_dmean3D, float* dL_dscale, float* dL_drot, hipStream_t s);
+
 }  // namespace gsr

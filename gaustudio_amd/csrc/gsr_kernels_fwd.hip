@@ -88,7 +88,9 @@ __device__ __forceinline__ void for_each_tile(bool active, int rminx, int rminy,
 }
 
 // ------------------------------------------------------------------------------------------------
-// SH -> RGB for one Gaussian (computeColorFromSH, forward.cu:20-71); returns the clamp mask.
+// SH -> RGB for one Gaussian (computeColorFromSH, forward.cu:20-71); returns the clamp mask.  gs_sh_eval (gsr_common.h) repeats
+// these operations for the surfel preprocess: a change here must be made there too (this copy stays as it is so that the 3DGS
+// kernels' code and results are untouched by the surfel operator).
 template <int D>
 __device__ __forceinline__ uint32_t gs_sh_to_rgb(const float* sh, float3 p_orig, const GsCam* __restrict__ cam, float* rgb)
 {

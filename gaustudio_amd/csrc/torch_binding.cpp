@@ -532,6 +532,104 @@ RasterizeGaussiansRawBackward(const torch::Tensor& background, const torch::Tens
 	return std::make_tuple(dL_dmeans2D, dL_dopacity, dL_dmeans3D, dL_df_dc, dL_df_rest, dL_dscales, dL_drotations);
 }
 
+// 2D Gaussian surfels (diff_surfel_rasterization._C): the forward returns
+// (num_rendered, color [3,H,W], radii [P], allmap [7,H,W], geomBuffer, binningBuffer, imgBuffer)
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeSurfels(const torch::Tensor& background, const torch::Tensor& means3D_, const torch::Tensor& colors_,
+                 const torch::Tensor& opacity_, const torch::Tensor& scales_, const torch::Tensor& rotations_, const float scale_modifier,
+                 const torch::Tensor& viewmatrix_, const torch::Tensor& projmatrix_, const int image_height, const int image_width,
+                 const torch::Tensor& sh_, const int degree, const torch::Tensor& campos_, const bool debug, const std::vector<int>& options)
+{
+	TORCH_CHECK(means3D_.ndimension() == 2 && means3D_.size(1) == 3, "means3D must have dimensions (num_points, 3)");
+	require_device(means3D_, "means3D");
+	const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+	const int P = means3D_.size(0), H = image_height, W = image_width;
+	const auto means3D = means3D_.contiguous(), colors = colors_.contiguous(), opacity = opacity_.contiguous();
+	const auto scales = scales_.contiguous(), rotations = rotations_.contiguous(), sh = sh_.contiguous();
+	const auto viewmatrix = viewmatrix_.contiguous(), projmatrix = projmatrix_.contiguous();
+	const auto campos = campos_.contiguous(), bg = background.contiguous();
+	check_rows(colors, P, 3, "colors_precomp");
+	TORCH_CHECK(opacity.numel() == P, "opacities must hold one value per surfel (got ", opacity.numel(), " for ", P, ")");
+	TORCH_CHECK(scales.numel() == 2 * (int64_t)P, "scales must have dimensions (num_points, 2)");
+	TORCH_CHECK(rotations.numel() == 4 * (int64_t)P, "rotations must have dimensions (num_points, 4)");
+	if (sh.numel() != 0)
+		TORCH_CHECK(sh.ndimension() == 3 && sh.size(0) == P && sh.size(2) == 3, "sh must have dimensions (num_points, M, 3)");
+	check_small(viewmatrix, 16, "viewmatrix");
+	check_small(projmatrix, 16, "projmatrix");
+	check_small(campos, 3, "campos");
+	check_small(bg, 3, "bg");
+	TORCH_CHECK(H > 0 && W > 0, "image size must be positive");
+	for (const auto& p : {std::make_pair(&colors, "colors_precomp"), std::make_pair(&opacity, "opacities"), std::make_pair(&scales, "scales"),
+	                      std::make_pair(&rotations, "rotations"), std::make_pair(&sh, "sh")})
+		if (p.first->numel() != 0) require_device(*p.first, p.second);
+	const auto fo = means3D.options().dtype(torch::kFloat32);
+	torch::Tensor out_color = torch::empty({3, H, W}, fo), out_allmap = torch::empty({7, H, W}, fo);
+	torch::Tensor radii = torch::empty({P}, means3D.options().dtype(torch::kInt32));
+	const auto bo = torch::TensorOptions(torch::kByte).device(means3D.device());
+	torch::Tensor geom = torch::empty({0}, bo), binning = torch::empty({0}, bo), img = torch::empty({0}, bo);
+	const int M = (sh.numel() != 0 && sh.size(0) != 0) ? (int)sh.size(1) : 0;
+	const gsr_options opt = make_options(options);
+	const int rc = gsr_surfel_forward(&opt, resize_cb, &geom, resize_cb, &binning, resize_cb, &img, P, degree, M, fptr(bg, "bg"), W, H,
+	                                  fptr(means3D, "means3D"), fptr(sh, "sh"), fptr(colors, "colors_precomp"), fptr(opacity, "opacities"),
+	                                  fptr(scales, "scales"), scale_modifier, fptr(rotations, "rotations"), fptr(viewmatrix, "viewmatrix"),
+	                                  fptr(projmatrix, "projmatrix"), fptr(campos, "campos"), out_color.data_ptr<float>(),
+	                                  out_allmap.data_ptr<float>(), P ? radii.data_ptr<int>() : nullptr, debug ? 1 : 0,
+	                                  current_stream(means3D));
+	if (rc < 0) fail(rc);
+	return std::make_tuple(rc, out_color, radii, out_allmap, geom, binning, img);
+}
+
+// -> (dL_dmeans2D [P,3], dL_dcolors [P,3], dL_dopacity [P,1], dL_dmeans3D [P,3], dL_dsh [P,M,3], dL_dscales [P,2], dL_drotations [P,4])
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeSurfelsBackward(const torch::Tensor& means3D_, const torch::Tensor& radii_, const torch::Tensor& colors_,
+                         const torch::Tensor& scales_, const torch::Tensor& rotations_, const float scale_modifier,
+                         const torch::Tensor& out_color_, const torch::Tensor& out_allmap_, const torch::Tensor& dL_dout_color,
+                         const torch::Tensor& dL_dout_allmap, const torch::Tensor& sh_, const int degree, const torch::Tensor& geomBuffer,
+                         const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug,
+                         const std::vector<int>& options)
+{
+	require_device(means3D_, "means3D");
+	const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+	const gsr_options opt = make_options(options);
+	const int P = means3D_.size(0);
+	TORCH_CHECK(out_color_.ndimension() == 3 && out_color_.size(0) == 3 && out_allmap_.ndimension() == 3 && out_allmap_.size(0) == 7,
+	            "out_color / out_allmap must be the [3,H,W] / [7,H,W] outputs of rasterize_surfels");
+	const int H = (int)out_color_.size(1), W = (int)out_color_.size(2);
+	const auto means3D = means3D_.contiguous(), colors = colors_.contiguous(), scales = scales_.contiguous();
+	const auto rotations = rotations_.contiguous(), sh = sh_.contiguous(), radii = radii_.contiguous();
+	const auto out_color = out_color_.contiguous(), out_allmap = out_allmap_.contiguous();
+	const auto g_color = dL_dout_color.contiguous(), g_allmap = dL_dout_allmap.contiguous();
+	const int M = (sh.numel() != 0 && sh.size(0) != 0) ? (int)sh.size(1) : 0;
+	TORCH_CHECK(g_color.numel() == 0 || (g_color.numel() == 3 * (int64_t)H * W && g_color.is_cuda()), "dL_dout_color must be [3,H,W] or empty");
+	TORCH_CHECK(g_allmap.numel() == 0 || (g_allmap.numel() == 7 * (int64_t)H * W && g_allmap.is_cuda()), "dL_dout_allmap must be [7,H,W] or empty");
+	check_rows(colors, P, 3, "colors_precomp");
+	check_rows(scales, P, 2, "scales");
+	check_rows(rotations, P, 4, "rotations");
+	check_rows(radii, P, 1, "radii");
+	TORCH_CHECK(R >= 0, "num_rendered must be non-negative");
+	const auto fo = means3D.options().dtype(torch::kFloat32);
+	torch::Tensor dL_dmeans2D = torch::empty({P, 3}, fo), dL_dcolors = torch::empty({P, 3}, fo), dL_dopacity = torch::empty({P, 1}, fo);
+	torch::Tensor dL_dmeans3D = torch::empty({P, 3}, fo), dL_dsh = torch::empty({M ? P : 0, M, 3}, fo);
+	torch::Tensor dL_dscales = torch::empty({P, 2}, fo), dL_drotations = torch::empty({P, 4}, fo);
+	if (P != 0) {
+		TORCH_CHECK(geomBuffer.is_cuda() && imageBuffer.is_cuda() && binningBuffer.is_cuda(), "the three opaque buffers must be the "
+		            "device tensors rasterize_surfels returned");
+		const auto bo = torch::TensorOptions(torch::kByte).device(means3D.device());
+		torch::Tensor scratch = torch::empty({(long long)gsr_surfel_scratch_bytes(P, R)}, bo);
+		const int rc = gsr_surfel_backward(&opt, P, degree, M, R, W, H, fptr(means3D, "means3D"), fptr(sh, "sh"), fptr(colors, "colors_precomp"),
+		                                   fptr(scales, "scales"), scale_modifier, fptr(rotations, "rotations"), radii.data_ptr<int>(),
+		                                   reinterpret_cast<const char*>(geomBuffer.data_ptr()), reinterpret_cast<const char*>(binningBuffer.data_ptr()),
+		                                   reinterpret_cast<const char*>(imageBuffer.data_ptr()), fptr(out_color, "out_color"),
+		                                   fptr(out_allmap, "out_allmap"), fptr(g_color, "dL_dout_color"), fptr(g_allmap, "dL_dout_allmap"),
+		                                   dL_dmeans2D.data_ptr<float>(), dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
+		                                   dL_dmeans3D.data_ptr<float>(), M ? dL_dsh.data_ptr<float>() : nullptr, dL_dscales.data_ptr<float>(),
+		                                   dL_drotations.data_ptr<float>(), reinterpret_cast<char*>(scratch.data_ptr()), debug ? 1 : 0,
+		                                   current_stream(means3D));
+		if (rc < 0) fail(rc);
+	}
+	return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dsh, dL_dscales, dL_drotations);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
 	// the reference's positional signatures, plus optional trailing arguments: the per-call options (gsr_options) and, for the
@@ -566,4 +664,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 	      py::arg("dL_dout_color"), py::arg("dL_dout_depth"), py::arg("dL_dout_median_depth"), py::arg("dL_dout_final_opacity"),
 	      py::arg("degree"), py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"),
 	      py::arg("debug"), py::arg("options") = no_opts, py::arg("image_height") = -1, py::arg("image_width") = -1);
+	m.def("rasterize_surfels", &RasterizeSurfels, py::arg("background"), py::arg("means3D"), py::arg("colors"), py::arg("opacity"),
+	      py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("viewmatrix"), py::arg("projmatrix"),
+	      py::arg("image_height"), py::arg("image_width"), py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("debug"),
+	      py::arg("options") = no_opts);
+	m.def("rasterize_surfels_backward", &RasterizeSurfelsBackward, py::arg("means3D"), py::arg("radii"), py::arg("colors"),
+	      py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("out_color"), py::arg("out_allmap"),
+	      py::arg("dL_dout_color"), py::arg("dL_dout_allmap"), py::arg("sh"), py::arg("degree"), py::arg("geomBuffer"), py::arg("R"),
+	      py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("options") = no_opts);
 }

@@ -459,6 +459,32 @@ int gsr_tsdf_mc_emit(const uint64_t* block_keys, uint64_t capacity, const uint64
                      const uint32_t* edge_flags, const uint32_t* block_vertex_offset, const uint32_t* block_triangle_offset,
                      uint32_t* vertex_base, float* vertices, int* triangles, void* stream);
 
+/* ---- 2D Gaussian surfels ("2DGS": the operator behind diff_surfel_rasterization) ----
+ * Additive to ABI 6.  The same allocator callbacks, stream and gsr_options as gsr_forward_ex (fast_exp is honoured; the binning
+ * options do not apply: surfels are binned into the reference's square tile rects).  scales are [P,2], rotations [P,4]
+ * (normalised inside), exactly one of shs [P,M,3] / colors_precomp [P,3].  Outputs: out_color [3,H,W] (composited colour + T bg),
+ * out_allmap [7,H,W] = {expected depth, alpha, normal xyz (view space), median depth, depth distortion}, radii [P].
+ * Returns the number of (tile, surfel) instances R (>= 0) or a negative GSR_ERR_*.  The forward reads R back before it sizes
+ * the binning buffer (one host wait per call).  Semantics and constants: INTEGRATION.md "2D Gaussian surfels". */
+int gsr_surfel_forward(const gsr_options* opt, gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn binning_alloc,
+                       void* binning_ctx, gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
+                       int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                       const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                       const float* viewmatrix, const float* projmatrix, const float* cam_pos, float* out_color, float* out_allmap,
+                       int* radii, int debug, void* stream);
+/* bytes of the `scratch` a gsr_surfel_backward of R instances needs (one 64-B row of partial sums per instance) */
+size_t gsr_surfel_scratch_bytes(int P, int R);
+/* Backward of gsr_surfel_forward: the three buffers it filled, its outputs out_color / out_allmap (the compositing backward walks
+ * front to back and needs the totals) and the upstream gradients dL_dout_color [3,H,W] / dL_dout_allmap [7,H,W] (NULL = zero).
+ * Writes dL_dmean2D [P,3] (the 2DGS densification proxy), dL_dopacity [P], dL_dcolor [P,3], dL_dmean3D [P,3], dL_dsh [P,M,3]
+ * (only with shs), dL_dscale [P,2], dL_drot [P,4].  No float atomics: the result is bit-identical from run to run. */
+int gsr_surfel_backward(const gsr_options* opt, int P, int D, int M, int R, int width, int height, const float* means3D,
+                        const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                        const float* rotations, const int* radii, const char* geom_buffer, const char* binning_buffer,
+                        const char* image_buffer, const float* out_color, const float* out_allmap, const float* dL_dout_color,
+                        const float* dL_dout_allmap, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                        float* dL_dsh, float* dL_dscale, float* dL_drot, char* scratch, int debug, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

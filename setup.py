@@ -21,7 +21,7 @@ setup(
     name="gaustudio-amd",
     version="0.1.0",
     description="MI355X-native (gfx950) differentiable 3D-Gaussian rasterizer, drop-in for gaustudio_diff_gaussian_rasterization",
-    packages=["gaustudio_amd", "gaustudio_diff_gaussian_rasterization"],
+    packages=["gaustudio_amd", "gaustudio_diff_gaussian_rasterization", "diff_surfel_rasterization"],
     package_data={"gaustudio_amd": ["*.so"]},
     include_package_data=True,
     cmdclass={"build_py": BuildWithNative},

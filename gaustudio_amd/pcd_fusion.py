@@ -1,0 +1,285 @@
+"""Normal fusion and point-cloud cleaning of gs-extract-pcd on the GPU, over an exact HIP kNN (csrc/gsr_knn.hip).
+
+Mirrors what gaustudio/scripts/extract_pcd.py does after its render loop, which the reference runs on the CPU
+(scipy cKDTree with a Python loop per fused point, Open3D):
+
+    records = view_records(median_map, final_opacity, world_normals, radius)      # :330-337, per view
+    fusion = NormalFusion(xyz); fusion.add_view(*records, extrinsics[:3, 3])     # :108-183 normal_fusion
+    unique_ids, normals = fusion.finalize()
+    keep = clean_point_cloud(xyz[unique_ids], normals)                            # :45-51
+
+Contract and quirks: INTEGRATION.md "gs-extract-pcd".  ROCm tensors only, no CPU fallback; every call runs on the
+current stream of the tensors' device.
+"""
+import ctypes
+import math
+
+import torch
+
+from . import _C
+
+MAX_K = 64
+
+_ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
+
+
+class _Workspace:
+    """gsr_alloc_fn for the duration of one call: hands out torch uint8 tensors (stream-ordered through torch's caching
+    allocator) and keeps them alive until the call has been enqueued."""
+
+    def __init__(self, device):
+        self.device = device
+        self.bufs = []
+        self.fn = _ALLOC_FN(self._alloc)
+
+    def _alloc(self, ctx, nbytes):
+        t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
+        self.bufs.append(t)
+        return t.data_ptr()
+
+
+def _device_tensor(name, t, shape_last=None, dtypes=(torch.float32,)):
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a torch tensor")
+    if shape_last is not None and (t.dim() != 2 or t.shape[1] != shape_last):
+        raise ValueError(f"{name} must have shape [N, {shape_last}], got {list(t.shape)}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be one of {[str(d) for d in dtypes]}, got {t.dtype}")
+    return t
+
+
+def _on_rocm(**tensors):
+    """Checked after the shapes, dtypes and k, so that those errors need no device."""
+    for name, t in tensors.items():
+        if t is not None and t.device.type != "cuda":
+            raise RuntimeError(f"{name} is on '{t.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
+
+
+def _check_k(k, n, what="k"):
+    if not isinstance(k, int) or isinstance(k, bool):
+        raise TypeError(f"{what} must be an int")
+    if k < 1 or k > MAX_K:
+        raise ValueError(f"{what} must be in [1, {MAX_K}], got {k}")
+    if k > n:
+        raise ValueError(f"{what} = {k} needs at least {k} points, got {n}")
+
+
+def _points(name, p):
+    return _device_tensor(name, p, 3, (torch.float32, torch.float64))
+
+
+def _rc(name, rc):
+    if rc < 0:
+        raise RuntimeError(f"{name} failed (rc={rc})")
+    return rc
+
+
+# ------------------------------------------------------------------------------------------------------------- kNN
+def knn(points, k, queries=None):
+    """Exact k nearest neighbours of each query (default: each point) among `points` [N,3] (float32, or float64 holding
+    float32 values): (dist2 [Q,k] float64, idx [Q,k] int64) in ascending (squared distance, index) order, the distances in
+    float64 from the float32 coordinates (what cKDTree computes on the same values).  1 <= k <= 64, k <= N."""
+    pts = _points("points", points)
+    q = None if queries is None else _points("queries", queries)
+    _check_k(k, pts.shape[0])
+    _on_rocm(points=pts, queries=q)
+    pts = pts.to(torch.float32).contiguous()
+    if q is not None:
+        if q.device != pts.device:
+            raise ValueError("queries and points must be on the same device")
+        q = q.to(torch.float32).contiguous()
+    nq = pts.shape[0] if q is None else q.shape[0]
+    dist2 = torch.empty((nq, k), dtype=torch.float64, device=pts.device)
+    idx = torch.empty((nq, k), dtype=torch.int64, device=pts.device)
+    ws = _Workspace(pts.device)
+    with torch.cuda.device(pts.device):
+        rc = _C.lib().gsr_knn(ws.fn, None, _C._ptr(pts), ctypes.c_int(pts.shape[0]), _C._ptr(q), ctypes.c_int(nq),
+                              ctypes.c_int(k), _C._ptr(dist2), _C._ptr(idx), _C._stream(pts.device))
+    if rc == -2:
+        raise ValueError("knn: a point coordinate is not finite")
+    _rc("gsr_knn", rc)
+    return dist2, idx
+
+
+# ------------------------------------------------------------------------------------------------------------- records
+def scene_radius(camera_centres):
+    """getNerfppNorm(cameras)["radius"] (datasets/utils.py:82-104): 1.1 * max_i |c_i - mean(c)| over the camera centres
+    [N,3] (tensor or array-like).  Returns a Python float (float64)."""
+    c = torch.as_tensor(camera_centres, dtype=torch.float64).reshape(-1, 3)
+    if c.shape[0] == 0:
+        raise ValueError("scene_radius needs at least one camera centre")
+    return float((c - c.mean(dim=0, keepdim=True)).norm(dim=1).max()) * 1.1
+
+
+def view_records(median_map, final_opacity, world_normals, scene_radius):
+    """The records of one view (extract_pcd.py:330-337): pixels with median depth < 0.8 * scene_radius, final opacity
+    > 0.5 and world_normals.sum(-1) > -3 (the -1 marker of masked normals is rotated first, so most masked pixels pass).
+    median_map: the operator's [3,H,W] median output (channel 0 median depth, channel 2 median Gaussian id);
+    final_opacity: [1,H,W] or [H,W]; world_normals: [H,W,3] (camera normals @ inverse(R).T).
+    Returns (ids int32 [n], normals float32 [n,3] = -world_normals, confidences float32 [n] = final opacity)."""
+    median_map = _device_tensor("median_map", median_map)
+    if median_map.dim() != 3 or median_map.shape[0] < 3:
+        raise ValueError("median_map must have shape [3, H, W]")
+    H, W = median_map.shape[1:]
+    op = _device_tensor("final_opacity", final_opacity).reshape(H, W)
+    wn = _device_tensor("world_normals", world_normals)
+    if wn.shape != (H, W, 3):
+        raise ValueError(f"world_normals must have shape [{H}, {W}, 3]")
+    _on_rocm(median_map=median_map, final_opacity=op, world_normals=wn)
+    valid = (median_map[0] < scene_radius * 0.8) & (op > 0.5)
+    valid = (wn.sum(dim=-1) > -3) & valid
+    return median_map[2].int()[valid], (-wn[valid]).contiguous(), op[valid].contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------- fusion
+class NormalFusion:
+    """normal_fusion (extract_pcd.py:108-183) with the records kept on the device: add_view() computes each record's
+    weight and appends {id, normal, weight} (20 B) to one growable buffer; finalize() groups by id (stable radix sort),
+    runs the two per-id reductions in record order in fp64 and the 10-NN exponential smoothing.  Bit-identical from run
+    to run."""
+
+    def __init__(self, xyz):
+        xyz = _device_tensor("xyz", xyz, 3)
+        _on_rocm(xyz=xyz)
+        self.xyz = xyz.contiguous()
+        self.device = xyz.device
+        self.num_records = 0
+        self.records = torch.empty((1 << 16, 5), dtype=torch.int32, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def add_view(self, ids, normals, confidences, w2c_translation):
+        """One view's records and the translation extrinsics[:3, 3] of its WORLD-TO-CAMERA matrix (the reference's
+        quirk: not the camera centre)."""
+        ids = _device_tensor("ids", ids, None, (torch.int32, torch.int64)).reshape(-1)
+        normals = _device_tensor("normals", normals, 3)
+        conf = _device_tensor("confidences", confidences).reshape(-1)
+        n = ids.shape[0]
+        if normals.shape[0] != n or conf.shape[0] != n:
+            raise ValueError("ids, normals and confidences must have the same length")
+        _on_rocm(ids=ids, normals=normals, confidences=conf)
+        if ids.device != self.device or normals.device != self.device or conf.device != self.device:
+            raise ValueError("records must be on the device of xyz")
+        t = torch.as_tensor(w2c_translation, dtype=torch.float32).detach().cpu().reshape(-1)
+        if t.shape[0] != 3:
+            raise ValueError("w2c_translation must have 3 elements")
+        if n == 0:
+            return
+        need = self.num_records + n
+        if need >= 2 ** 31:
+            raise ValueError("NormalFusion holds at most 2^31 - 1 records")
+        if need > self.records.shape[0]:
+            grown = torch.empty((max(need, 2 * self.records.shape[0]), 5), dtype=torch.int32, device=self.device)
+            grown[:self.num_records] = self.records[:self.num_records]
+            self.records = grown
+        ids = ids.to(torch.int32).contiguous()
+        normals = normals.contiguous()
+        conf = conf.contiguous()
+        tc = (ctypes.c_float * 3)(*[float(v) for v in t.tolist()])
+        with torch.cuda.device(self.device):
+            rc = _C.lib().gsr_fusion_records(_C._ptr(self.xyz), ctypes.c_int(self.xyz.shape[0]), _C._ptr(ids), _C._ptr(normals),
+                                             _C._ptr(conf), ctypes.c_int(n), tc, _C._ptr(self.records[self.num_records:]),
+                                             _C._ptr(self.status), _C._stream(self.device))
+        _rc("gsr_fusion_records", rc)
+        self.num_records = need
+
+    def finalize(self, k=10, sigma=0.1, consistency=0.8):
+        """-> (unique_ids int32 [U] ascending, normals float32 [U,3]).  Raises ValueError with fewer than k fused points
+        (the reference's cKDTree query fails there)."""
+        if not isinstance(k, int) or k < 1 or k > MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        if int(self.status.item()) & 1:
+            raise ValueError(f"a record's id lies outside [0, {self.xyz.shape[0]})")
+        n = self.num_records
+        cap = max(min(n, self.xyz.shape[0]), 1)
+        uids = torch.empty(cap, dtype=torch.int32, device=self.device)
+        mean = torch.empty((cap, 3), dtype=torch.float32, device=self.device)
+        L = _C.lib()
+        with torch.cuda.device(self.device):
+            st = _C._stream(self.device)
+            ws = _Workspace(self.device)
+            U = _rc("gsr_fusion_group", L.gsr_fusion_group(ws.fn, None, _C._ptr(self.records), ctypes.c_int(n),
+                                                           ctypes.c_int(self.xyz.shape[0]), ctypes.c_float(consistency),
+                                                           _C._ptr(uids), _C._ptr(mean), st))
+            if U < k:
+                raise ValueError(f"normal fusion needs at least k = {k} fused points for the smoothing, got {U}")
+            uids, mean = uids[:U], mean[:U]
+            out = torch.empty((U, 3), dtype=torch.float32, device=self.device)
+            ws2 = _Workspace(self.device)
+            _rc("gsr_fusion_smooth", L.gsr_fusion_smooth(ws2.fn, None, _C._ptr(self.xyz), _C._ptr(uids), _C._ptr(mean),
+                                                         ctypes.c_int(U), ctypes.c_int(k), ctypes.c_float(sigma),
+                                                         _C._ptr(out), st))
+        return uids, out
+
+
+def normal_fusion(xyz, all_ids_list, all_normals_list, all_confidences_list, translations, k=10, sigma=0.1, consistency=0.8):
+    """The reference's normal_fusion(pcd, ids, normals, confidences, cameras) in one call, with `translations` the
+    per-view extrinsics[:3, 3] (world-to-camera translations) in place of the cameras."""
+    f = NormalFusion(xyz)
+    for ids, nrm, conf, t in zip(all_ids_list, all_normals_list, all_confidences_list, translations):
+        f.add_view(ids, nrm, conf, t)
+    return f.finalize(k=k, sigma=sigma, consistency=consistency)
+
+
+# ------------------------------------------------------------------------------------------------------------- cleaning
+def statistical_outlier_mask(points, nb_neighbors=50, std_ratio=2.0, return_distances=False):
+    """Open3D remove_statistical_outlier(nb_neighbors, std_ratio) as a keep mask (bool [N]); with return_distances also
+    the per-point mean kNN distance (float64 [N])."""
+    pts = _points("points", points)
+    n = pts.shape[0]
+    if not isinstance(nb_neighbors, int) or nb_neighbors < 1 or nb_neighbors > MAX_K:
+        raise ValueError(f"nb_neighbors must be in [1, {MAX_K}], got {nb_neighbors}")
+    _on_rocm(points=pts)
+    pts = pts.to(torch.float32).contiguous()
+    keep = torch.zeros(n, dtype=torch.uint8, device=pts.device)
+    dist = torch.empty(n, dtype=torch.float64, device=pts.device) if return_distances else None
+    if n:
+        ws = _Workspace(pts.device)
+        with torch.cuda.device(pts.device):
+            rc = _C.lib().gsr_outlier_statistical(ws.fn, None, _C._ptr(pts), ctypes.c_int(n), ctypes.c_int(nb_neighbors),
+                                                  ctypes.c_double(std_ratio), _C._ptr(keep), _C._ptr(dist),
+                                                  _C._stream(pts.device))
+        if rc == -2:
+            raise ValueError("statistical_outlier_mask: a point coordinate is not finite")
+        _rc("gsr_outlier_statistical", rc)
+    return (keep.bool(), dist) if return_distances else keep.bool()
+
+
+def normal_outlier_mask(points, normals, nb_neighbors=20, angle_threshold=math.pi / 4):
+    """remove_normal_outliers (extract_pcd.py:30-43) as a keep mask (bool [N]): neighbour 0 is dropped as the point
+    itself; keep where mean(acos(|n_j . n_i|)) < angle_threshold, in float64."""
+    pts = _points("points", points)
+    nrm = _device_tensor("normals", normals, 3, (torch.float32, torch.float64))
+    n = pts.shape[0]
+    if nrm.shape[0] != n:
+        raise ValueError("normals must have one row per point")
+    if not isinstance(nb_neighbors, int) or nb_neighbors < 1 or nb_neighbors > MAX_K:
+        raise ValueError(f"nb_neighbors must be in [1, {MAX_K}], got {nb_neighbors}")
+    _on_rocm(points=pts, normals=nrm)
+    pts = pts.to(torch.float32).contiguous()
+    keep = torch.zeros(n, dtype=torch.uint8, device=pts.device)
+    if n:
+        nrm = nrm.to(torch.float64).contiguous()
+        ws = _Workspace(pts.device)
+        with torch.cuda.device(pts.device):
+            rc = _C.lib().gsr_outlier_normal(ws.fn, None, _C._ptr(pts), _C._ptr(nrm), ctypes.c_int(n),
+                                             ctypes.c_int(nb_neighbors), ctypes.c_double(angle_threshold), _C._ptr(keep),
+                                             _C._stream(pts.device))
+        if rc == -2:
+            raise ValueError("normal_outlier_mask: a point coordinate is not finite")
+        _rc("gsr_outlier_normal", rc)
+    return keep.bool()
+
+
+def clean_point_cloud(points, normals, nb_neighbors=50, std_ratio=2.0, normal_neighbors=20, angle_threshold=math.pi / 4):
+    """clean_point_cloud (extract_pcd.py:45-51): the statistical test, then the normal test on the points it kept (the
+    kNN rebuilt over that subset).  Returns the kept indices into `points` (int64, ascending)."""
+    pts = _points("points", points)
+    nrm = _device_tensor("normals", normals, 3, (torch.float32, torch.float64))
+    if nrm.shape[0] != pts.shape[0]:
+        raise ValueError("normals must have one row per point")
+    _on_rocm(points=pts, normals=nrm)
+    first = torch.nonzero(statistical_outlier_mask(pts, nb_neighbors, std_ratio)).flatten()
+    if first.numel() == 0:
+        return first
+    second = normal_outlier_mask(pts[first], nrm[first], normal_neighbors, angle_threshold)
+    return first[second]

@@ -485,6 +485,57 @@ int gsr_surfel_backward(const gsr_options* opt, int P, int D, int M, int R, int 
                         const float* dL_dout_allmap, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                         float* dL_dsh, float* dL_dscale, float* dL_drot, char* scratch, int debug, void* stream);
 
+/* ---- nearest neighbours, normal fusion and outlier removal: what gs-extract-pcd does after its render loop
+ * (gaustudio/scripts/extract_pcd.py:108-183 normal_fusion, :30-51 clean_point_cloud; scipy cKDTree and Open3D on the CPU in
+ * the reference).  Additive to ABI 6.  Stateless: inputs and outputs are caller-owned device memory, scratch comes from the
+ * gsr_alloc_fn callback (called once or twice per call, device memory that must stay valid until the call's work on `stream`
+ * has run), `stream` is the HIP stream of every launch.  Each entry reads a few values back to the host (the grid's cell
+ * count, the number of fused ids), so it waits on `stream` once or more.  Returns GSR_OK (or a count, where stated) or
+ * a negative GSR_ERR_*.  Algorithms, resources and parity status: gaustudio_amd/csrc/gsr_knn.hip, DESIGN.md s11,
+ * INTEGRATION.md "gs-extract-pcd". ---- */
+#define GSR_KNN_MAX_K 64
+
+/* Exact k nearest neighbours: for each of queries[num_queries,3] (NULL = the points themselves; num_queries is then
+ * ignored) the k nearest of points[num_points,3] (f32, all finite), 1 <= k <= min(64, num_points), in ascending
+ * (squared distance, index) order: dist2[num_queries,k] (f64, computed from the f32 coordinates) and indices[num_queries,k]
+ * (i64).  A query point that is also a data point finds itself first unless a duplicate with a lower index ties with it.
+ * GSR_ERR_ARG for a bad k or a non-finite point coordinate. */
+int gsr_knn(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, const float* queries,
+            int num_queries, int k, double* dist2, int64_t* indices, void* stream);
+
+/* normal_fusion, per view (extract_pcd.py:118-126): for record i = (ids[i], normals[i,3], confidences[i]) of one view,
+ * v = w2c_translation - xyz[ids[i]] (w2c_translation = extrinsics[:3,3] of the world-to-camera matrix, HOST float[3]) and
+ * w = conf * |dot(v / |v|, n)| / (|v| + 1e-6) (fp64, stored f32).  Writes records[num_records,5] = {id, n.x, n.y, n.z, w}
+ * (the id as int32, the rest as f32 bits).  An id outside [0, num_gaussians) sets bit 0 of status[1] (u32, caller-zeroed). */
+int gsr_fusion_records(const float* xyz, int num_gaussians, const int* ids, const float* normals, const float* confidences,
+                       int num_records, const float w2c_translation[3], int* records, int* status, void* stream);
+
+/* normal_fusion, steps 1-3 (extract_pcd.py:109-168): groups records[num_records,5] by id (stable radix sort, so an id's
+ * records are reduced in record order), and per id mean = normalize(sum n w / sum w) in fp64, then the same over the
+ * records with |n - mean| < consistency (0/0 = NaN where none is consistent; kept).  Writes unique_ids[U] (ascending) and
+ * mean_normals[U,3] (f32); both must hold min(num_records, num_gaussians) entries.  Returns U >= 0. */
+int gsr_fusion_group(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const int* records, int num_records, int num_gaussians,
+                     float consistency, int* unique_ids, float* mean_normals, void* stream);
+
+/* normal_fusion, step 4 (extract_pcd.py:170-181): q = xyz[unique_ids]; per fused point its k nearest points of q (itself
+ * included), s = sum_j mean_normals[nbr_j] * exp(-sqrt(d2_j) / sigma) in fp64, cast to f32, normals[U,3] = s / max(|s|,
+ * 1e-12) in f32.  A NaN neighbour makes the point NaN.  GSR_ERR_ARG when num_unique < k. */
+int gsr_fusion_smooth(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* xyz, const int* unique_ids,
+                      const float* mean_normals, int num_unique, int k, float sigma, float* normals, void* stream);
+
+/* Open3D PointCloud::RemoveStatisticalOutliers(nb_neighbors, std_ratio) as restated in INTEGRATION.md: a_i = mean of the
+ * distances to the min(nb_neighbors, num_points) nearest points (itself included, at 0); mean and Bessel-corrected std over
+ * the points with a_i > 0 (fixed-order fp64 reductions); keep[i] = 0 < a_i < mean + std_ratio * std (u8).
+ * mean_distance[num_points] (f64, NULL = not wanted) receives a_i. */
+int gsr_outlier_statistical(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points,
+                            int nb_neighbors, double std_ratio, unsigned char* keep, double* mean_distance, void* stream);
+
+/* remove_normal_outliers (extract_pcd.py:30-43): with the min(nb_neighbors, num_points) nearest points, neighbour 0 taken to
+ * be the point itself and dropped, keep[i] = mean_j acos(|dot(n_j, n_i)|) < angle_threshold (fp64; a NaN mean drops the
+ * point).  normals[num_points,3] f64. */
+int gsr_outlier_normal(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, const double* normals,
+                       int num_points, int nb_neighbors, double angle_threshold, unsigned char* keep, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

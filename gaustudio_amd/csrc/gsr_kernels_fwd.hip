@@ -1960,6 +1960,9 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
 // FX: exp on the transcendental unit (gs_exp_hw) instead of the reproducible 9-instruction gs_exp -- the opt-in
 // `fast_exp` mode (docs/DESIGN_history_r1-r4.md s4.5): outputs then agree with the bit-exact mode to ~1e-6 relative except at threshold
 // flips (tests/test_gpu_fastexp.py attributes every one of them), and the backward must run in the same mode.
+#ifndef GSR_FWD_MED_SPLIT
+#define GSR_FWD_MED_SPLIT 1  // 0: the walk keeps the median bookkeeping in every step (the A/B baseline of the phase split)
+#endif
 #ifndef GSR_FWD_WAVES
 #define GSR_FWD_WAVES 7      // waves per SIMD the register allocation is held to
 #endif
@@ -2007,6 +2010,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_FWD_WAV
 	v2f acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
 	uint32_t med_pos = 0;
 	float med_T = 0.f;
+#if GSR_FWD_MED_SPLIT
+	// wave-uniform: some lane may still record a median candidate.  The walk runs the step with the median bookkeeping (a
+	// compare and two selects) only while this holds, then a copy without it for the rest of the tile: same bits by construction
+	bool med_live = true;
+#endif
 	if (tid < 3) sRec[tid * GSR_FWD_PLANE + 256] = make_float4(0.f, 0.f, 0.f, 0.f);   // opacity 0: alpha = 0, never valid
 	const char* rec_base = reinterpret_cast<const char*>(sRec);
 	const uint16_t* my_list = &sList[w][q][0];
@@ -2067,37 +2075,64 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_FWD_WAV
 		// four list entries per step, fetched one step ahead of their use; the scheduling barrier keeps the read up here
 		// (left alone, the scheduler sinks it to its use and exposes a full LDS latency per step)
 		uint2 pk = *reinterpret_cast<const uint2*>(my_list);
-		for (int i = 0; i < n; i += 4) {
-			if ((i & 31) == 0 && __ballot(!done) == 0ull) break;   // every pixel of this wave has saturated
-			const uint32_t offs[4] = {pk.x & 0xffffu, pk.x >> 16, pk.y & 0xffffu, pk.y >> 16};
-			pk = *reinterpret_cast<const uint2*>(my_list + i + 4);
-			__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				const uint32_t off = offs[k];
-				const float4 A = *reinterpret_cast<const float4*>(rec_base + off);
-				const float4 B = *reinterpret_cast<const float4*>(rec_base + off + GSR_FWD_PLANE * 16);
-				const float4 Cc = *reinterpret_cast<const float4*>(rec_base + off + 2 * GSR_FWD_PLANE * 16);
-				const float dx = A.x - pixfx, dy = A.y - pixfy;
-				const float power = FMA(A.w * dx, dy, FMA(B.x * dy, dy, (A.z * dx) * dx));
-				const float alpha = fminf(0.99f, B.y * (FX ? gs_exp_hw(power) : gs_exp(power)));
-				// FX: gs_exp_hw is valid for every power <= 0 and power < pcut implies alpha < 1/255 (preprocess): the pcut
-				// pre-test is implied by the alpha test, as in composite_bwd's FX arm -- one compare and one LDS read less per step
-				const bool valid = (!done) & (power <= 0.0f) & (FX ? true : (power >= (NOCULL ? -80.0f : B.w))) & (!(alpha < 1.0f / 255.0f));
-				const float test_T = T_ * (1 - alpha);
-				const bool stop = valid & (test_T < 0.0001f);
-				done = done | stop;
-				const bool apply = valid & (!stop);
-				const float wgt = apply ? alpha * T_ : 0.f;
-				acc01 = vfma(v2f{Cc.x, Cc.y}, v2f{wgt, wgt}, acc01);
-				acc23 = vfma(v2f{Cc.z, Cc.w}, v2f{wgt, wgt}, acc23);
-				const bool medc = apply & (T_ > 0.5f);
-				med_off = medc ? off : med_off;
-				med_T = medc ? T_ : med_T;
-				T_ = apply ? test_T : T_;
-				last_off = apply ? off : last_off;
+		// one group of four steps; MED: with the median bookkeeping (see med_live).  A macro, not a lambda: with `done` captured
+		// by reference the compiler keeps it as a byte in a VGPR (about four more VALU per step) instead of a lane mask.
+		// FX: gs_exp_hw is valid for every power <= 0 and power < pcut implies alpha < 1/255 (preprocess): the pcut pre-test is
+		// implied by the alpha test, as in composite_bwd's FX arm -- one compare and one LDS read less per step
+#define GSR_FWD_GROUP(MED)                                                                                                   \
+	{                                                                                                                        \
+		const uint32_t offs[4] = {pk.x & 0xffffu, pk.x >> 16, pk.y & 0xffffu, pk.y >> 16};                                   \
+		pk = *reinterpret_cast<const uint2*>(my_list + i + 4);                                                               \
+		__builtin_amdgcn_sched_barrier(0);                                                                                   \
+		_Pragma("unroll") for (int k = 0; k < 4; k++) {                                                                      \
+			const uint32_t off = offs[k];                                                                                    \
+			const float4 A = *reinterpret_cast<const float4*>(rec_base + off);                                               \
+			const float4 B = *reinterpret_cast<const float4*>(rec_base + off + GSR_FWD_PLANE * 16);                          \
+			const float4 Cc = *reinterpret_cast<const float4*>(rec_base + off + 2 * GSR_FWD_PLANE * 16);                     \
+			const float dx = A.x - pixfx, dy = A.y - pixfy;                                                                  \
+			const float power = FMA(A.w * dx, dy, FMA(B.x * dy, dy, (A.z * dx) * dx));                                      \
+			const float alpha = fminf(0.99f, B.y * (FX ? gs_exp_hw(power) : gs_exp(power)));                                 \
+			const bool valid = (!done) & (power <= 0.0f) & (FX ? true : (power >= (NOCULL ? -80.0f : B.w))) &                \
+			                   (!(alpha < 1.0f / 255.0f));                                                                   \
+			const float test_T = T_ * (1 - alpha);                                                                           \
+			const bool stop = valid & (test_T < 0.0001f);                                                                    \
+			done = done | stop;                                                                                              \
+			const bool apply = valid & (!stop);                                                                              \
+			const float wgt = apply ? alpha * T_ : 0.f;                                                                      \
+			acc01 = vfma(v2f{Cc.x, Cc.y}, v2f{wgt, wgt}, acc01);                                                             \
+			acc23 = vfma(v2f{Cc.z, Cc.w}, v2f{wgt, wgt}, acc23);                                                             \
+			if (MED) {                                                                                                       \
+				const bool medc = apply & (T_ > 0.5f);                                                                       \
+				med_off = medc ? off : med_off;                                                                              \
+				med_T = medc ? T_ : med_T;                                                                                   \
+			}                                                                                                                \
+			T_ = apply ? test_T : T_;                                                                                        \
+			last_off = apply ? off : last_off;                                                                               \
+		}                                                                                                                    \
+	}
+#if GSR_FWD_MED_SPLIT
+		int i = 0;
+		if (med_live) {
+			for (; i < n; i += 4) {
+				// T_ never rises and done never clears: once no lane of the wave is both live and above 0.5, medc is false in every
+				// later step of the tile, this batch and the next ones.  (A wave that has saturated ends this phase too.)
+				if (__builtin_amdgcn_ballot_w64((!done) & (T_ > 0.5f)) == 0ull) { med_live = false; break; }
+				GSR_FWD_GROUP(true)
 			}
 		}
+		if (!med_live && __builtin_amdgcn_ballot_w64(!done) != 0ull) {
+			for (; i < n; i += 4) {
+				if ((i & 31) == 0 && __ballot(!done) == 0ull) break;   // every pixel of this wave has saturated
+				GSR_FWD_GROUP(false)
+			}
+		}
+#else
+		for (int i = 0; i < n; i += 4) {
+			if ((i & 31) == 0 && __ballot(!done) == 0ull) break;   // every pixel of this wave has saturated
+			GSR_FWD_GROUP(true)
+		}
+#endif
+#undef GSR_FWD_GROUP
 		if (last_off != GSR_FWD_NONE) last_contributor = (uint32_t)base + (last_off >> 4) + 1u;
 		if (med_off != GSR_FWD_NONE) med_pos = (uint32_t)base + (med_off >> 4) + 1u;
 	}

@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "../../include/gsrast.h"
+#include "gsr_sort.h"
 
 namespace {
 
@@ -378,75 +379,6 @@ char* ws_alloc(gsr_alloc_fn alloc, void* ctx, size_t bytes)
 	return alloc ? alloc(ctx, bytes) : nullptr;
 }
 
-// ------------------------------------------------------------------------------------------------------ scans
-// exclusive scan of n ints in three passes over 1024-element tiles; `part` holds ceil(n/1024) + 1 ints; total in out[n]
-__global__ void __launch_bounds__(256) tile_sums(const int* __restrict__ in, int n, int* __restrict__ part)
-{
-	__shared__ int red[256];
-	const int base = blockIdx.x * 1024;
-	int s = 0;
-	for (int j = 0; j < 4; j++) {
-		const int i = base + j * 256 + threadIdx.x;
-		if (i < n) s += in[i];
-	}
-	red[threadIdx.x] = s;
-	__syncthreads();
-	for (int w = 128; w > 0; w >>= 1) {
-		if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-__global__ void __launch_bounds__(1024) scan_parts(int* part, int np)
-{
-	__shared__ int buf[1024];
-	int carry = 0;
-	for (int b = 0; b < np; b += 1024) {
-		const int i = b + threadIdx.x;
-		const int v = i < np ? part[i] : 0;
-		buf[threadIdx.x] = v;
-		__syncthreads();
-		for (int o = 1; o < 1024; o <<= 1) {
-			const int y = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
-			__syncthreads();
-			buf[threadIdx.x] += y;
-			__syncthreads();
-		}
-		if (i < np) part[i] = carry + buf[threadIdx.x] - v;
-		const int tot = buf[1023];
-		__syncthreads();
-		carry += tot;
-	}
-	if (threadIdx.x == 0) part[np] = carry;
-}
-__global__ void __launch_bounds__(1024) scan_tiles(const int* __restrict__ in, int n, const int* __restrict__ part, int np,
-                                                   int* __restrict__ out)
-{
-	__shared__ int buf[1024];
-	const int i = blockIdx.x * 1024 + threadIdx.x;
-	const int v = i < n ? in[i] : 0;
-	buf[threadIdx.x] = v;
-	__syncthreads();
-	for (int o = 1; o < 1024; o <<= 1) {
-		const int y = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
-		__syncthreads();
-		buf[threadIdx.x] += y;
-		__syncthreads();
-	}
-	if (i < n) out[i] = part[blockIdx.x] + buf[threadIdx.x] - v;
-	if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = part[np];
-}
-// out[n + 1]: exclusive scan and total
-int exclusive_scan(const int* in, int n, int* out, int* part, hipStream_t s)
-{
-	const int np = (n + 1023) / 1024;
-	if (np == 0) return hipMemsetAsync(out, 0, sizeof(int), s) == hipSuccess ? GSR_OK : GSR_ERR_HIP;
-	hipLaunchKernelGGL(tile_sums, dim3(np), dim3(256), 0, s, in, n, part);
-	hipLaunchKernelGGL(scan_parts, dim3(1), dim3(1024), 0, s, part, np);
-	hipLaunchKernelGGL(scan_tiles, dim3(np), dim3(1024), 0, s, in, n, part, np, out);
-	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
-}
-
 // ------------------------------------------------------------------------------------------------------ fusion
 // record = 5 words {id (int), n.x, n.y, n.z, w}
 __global__ void __launch_bounds__(256) fusion_records(const float* __restrict__ xyz, int P, const int* __restrict__ ids,
@@ -481,62 +413,6 @@ __global__ void __launch_bounds__(256) sort_init(const int* __restrict__ rec, in
 	if (i >= n) return;
 	keys[i] = rec[5 * (size_t)i];
 	vals[i] = i;
-}
-
-constexpr int RADIX_ITEMS = 16;   // items per thread of a 256-thread tile: 4096 keys
-
-// hist[digit * ntiles + tile]
-__global__ void __launch_bounds__(256) radix_hist(const int* __restrict__ keys, int n, int shift, int ntiles, int* __restrict__ hist)
-{
-	__shared__ int h[256];
-	h[threadIdx.x] = 0;
-	__syncthreads();
-	const int base = blockIdx.x * 256 * RADIX_ITEMS;
-	for (int j = 0; j < RADIX_ITEMS; j++) {
-		const int i = base + j * 256 + threadIdx.x;
-		if (i < n) atomicAdd(&h[((unsigned)keys[i] >> shift) & 255], 1);
-	}
-	__syncthreads();
-	hist[threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// stable scatter: items keep their order within a digit (rounds in order, waves in order, lanes in order)
-__global__ void __launch_bounds__(256) radix_scatter(const int* __restrict__ keys, const int* __restrict__ vals, int n, int shift,
-                                                     int ntiles, const int* __restrict__ offs, int* __restrict__ okeys,
-                                                     int* __restrict__ ovals)
-{
-	__shared__ int base[256];
-	__shared__ int wcnt[4][256];
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	base[threadIdx.x] = offs[threadIdx.x * ntiles + blockIdx.x];
-	for (int w = 0; w < 4; w++) wcnt[w][threadIdx.x] = 0;
-	__syncthreads();
-	const int tile = blockIdx.x * 256 * RADIX_ITEMS;
-	const uint64_t lt = (1ull << lane) - 1;
-	for (int j = 0; j < RADIX_ITEMS; j++) {
-		const int i = tile + j * 256 + threadIdx.x;
-		const bool valid = i < n;
-		const int key = valid ? keys[i] : 0;
-		const int digit = ((unsigned)key >> shift) & 255;
-		uint64_t peers = __ballot(valid);
-		for (int b = 0; b < 8; b++) {
-			const uint64_t m = __ballot(valid && ((digit >> b) & 1));
-			peers &= ((digit >> b) & 1) ? m : ~m;
-		}
-		const int rank = __popcll(peers & lt);
-		if (valid && (peers >> lane) == 1) wcnt[wave][digit] = __popcll(peers);   // the digit's last lane in this wave
-		__syncthreads();
-		if (valid) {
-			int pos = base[digit] + rank;
-			for (int w = 0; w < wave; w++) pos += wcnt[w][digit];
-			okeys[pos] = key;
-			ovals[pos] = vals[i];
-		}
-		__syncthreads();
-		base[threadIdx.x] += wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] + wcnt[3][threadIdx.x];
-		for (int w = 0; w < 4; w++) wcnt[w][threadIdx.x] = 0;
-		__syncthreads();
-	}
 }
 
 __global__ void __launch_bounds__(256) unique_flags(const int* __restrict__ keys, int n, int* __restrict__ flags)
@@ -758,10 +634,10 @@ int gsr_fusion_group(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const in
 	int bits = 1;
 	while (bits < 31 && (1LL << bits) < num_gaussians) bits++;
 	for (int shift = 0; shift < bits; shift += 8) {
-		hipLaunchKernelGGL(radix_hist, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, hist);
+		hipLaunchKernelGGL(radix_hist<int>, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, hist);
 		const int rc = exclusive_scan(hist, (int)nh, offs, part, s);
 		if (rc) return rc;
-		hipLaunchKernelGGL(radix_scatter, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, offs, k1, v1);
+		hipLaunchKernelGGL(radix_scatter<int>, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, offs, k1, v1);
 		int* t = k0; k0 = k1; k1 = t;
 		t = v0; v0 = v1; v1 = t;
 	}

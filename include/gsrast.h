@@ -536,6 +536,42 @@ int gsr_outlier_statistical(gsr_alloc_fn workspace_alloc, void* workspace_ctx, c
 int gsr_outlier_normal(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, const double* normals,
                        int num_points, int nb_neighbors, double angle_threshold, unsigned char* keep, void* stream);
 
+/* ---- triangle mesh rasterization: what gaustudio/scripts/render_mesh.py and texture_mesh.py take from PyTorch3D
+ * (MeshRasterizer with blur_radius = 0, faces_per_pixel = 1: a hard z-buffer; interpolate_face_attributes;
+ * Meshes.verts_normals_packed; get_visible_faces).  Additive to ABI 6, in the style of gsr_knn: inputs and outputs are
+ * caller-owned device memory, scratch comes from the gsr_alloc_fn callback (called once or twice per call), `stream` is the
+ * HIP stream of every launch; each entry reads a count or an error flag back, so it waits on `stream` once.  Forward only,
+ * deterministic (no float atomics; bit-identical from run to run).  Contract: INTEGRATION.md s15; design: gsr_mesh.hip,
+ * DESIGN.md s12. ---- */
+#define GSR_MESH_MAX_CHANNELS 4
+
+/* verts[num_verts,3] f32 world space, faces[num_faces,3] i32; intrinsics = 3x3 row-major K (fx, fy, cx, cy are read) and
+ * extrinsics = 4x4 row-major world-to-camera matrix (OpenCV axes, Camera.extrinsics), both HOST pointers.  Pixel (i, j) casts
+ * the camera-space ray ((j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy, 1); each pixel keeps the hit with the least (z, face id),
+ * a hit counting when z > z_near (z_near >= 0).  cull_backfaces != 0 keeps the faces with ((b - a) x (c - a)) . a < 0 in
+ * camera space.  Outputs pix_to_face[H,W] i32, zbuf[H,W] f32 (camera z), bary[H,W,3] f32 (perspective-correct), -1 on
+ * background.  Returns the number of (tile, face) entries binned (>= 0), or GSR_ERR_ARG for a face index outside
+ * [0, num_verts), a non-positive or too large (> 16384) size, singular or non-finite intrinsics, a negative z_near. */
+int gsr_mesh_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* verts, int num_verts, const int* faces,
+                       int num_faces, const float intrinsics[9], const float extrinsics[16], int height, int width,
+                       int cull_backfaces, float z_near, int* pix_to_face, float* zbuf, float* bary, void* stream);
+
+/* interpolate_face_attributes for per-vertex attributes: out[p,c] = (b0 attr[f0,c] + b1 attr[f1,c]) + b2 attr[f2,c] with
+ * (f0, f1, f2) = faces[pix_to_face[p]] and (b0, b1, b2) = bary[p]; 0 where pix_to_face[p] < 0.  attr[num_verts,channels],
+ * 1 <= channels <= GSR_MESH_MAX_CHANNELS.  GSR_ERR_ARG when a face id >= num_faces or a face index is out of range. */
+int gsr_mesh_interpolate(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const int* faces, int num_faces, const int* pix_to_face,
+                         const float* bary, int num_pixels, const float* attr, int num_verts, int channels, float* out, void* stream);
+
+/* Meshes.verts_normals_packed: corner k of face f adds (v[k+1] - v[k]) x (v[k+2] - v[k]) (indices mod 3) to its vertex, in
+ * ascending (f, k) order in f32; normals[num_verts,3] = n / max(|n|, 1e-6).  GSR_ERR_ARG for a face index out of range. */
+int gsr_mesh_vertex_normals(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* verts, int num_verts, const int* faces,
+                            int num_faces, float* normals, void* stream);
+
+/* visible[num_faces] u8 = 1 for the faces that appear in pix_to_face[num_pixels], 0 elsewhere (texture_mesh.py
+ * get_visible_faces as a mask).  GSR_ERR_ARG when a face id >= num_faces. */
+int gsr_mesh_visible_faces(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const int* pix_to_face, int num_pixels, int num_faces,
+                           unsigned char* visible, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

@@ -5,7 +5,11 @@
                                  ->  TSDFVolume.integrate                         ->  extract_triangle_mesh -> PLY
 
 Runs on a synthetic shell of Gaussians written to / read back from the reference's on-disk formats, so it needs no
-dataset:   python examples/extract_mesh_synthetic.py [out_dir]
+dataset:   python examples/extract_mesh_synthetic.py [out_dir] [--clean]
+
+--clean (extract_mesh.py:149-186): the scene gets a small detached blob of Gaussians, the mesh is clustered into connected
+components and the clusters with at most half the triangles of the largest one are removed, all on the device
+(gaustudio_amd.mesh_clean); the result is written as fused_mesh.ply.
 """
 import json
 import math
@@ -21,13 +25,19 @@ from gaustudio_amd import GaussianRasterizationSettings, GaussianRasterizer, for
 from gaustudio_amd.tsdf import TSDFVolume  # noqa: E402
 
 
-def write_inputs(out):
+def write_inputs(out, floater=False):
     g = torch.Generator().manual_seed(0)
     P = 200_000
     d = torch.randn(P, 3, generator=g)
     d = d / d.norm(dim=1, keepdim=True)
     bumps = 1.0 + 0.08 * torch.sin(5 * d[:, 0:1]) * torch.cos(4 * d[:, 1:2])
-    cloud = formats.GaussianCloud(xyz=d * bumps, f_dc=(torch.rand(P, 1, 3, generator=g) - 0.5) / 0.28209479177387814,
+    xyz = d * bumps
+    if floater:                                   # a detached shell of radius 0.12 beside the object: something to remove
+        Q = 6_000
+        e = torch.randn(Q, 3, generator=g)
+        xyz = torch.cat([xyz, 0.12 * e / e.norm(dim=1, keepdim=True) + torch.tensor([1.5, 0.3, 0.0])])
+        P += Q
+    cloud = formats.GaussianCloud(xyz=xyz, f_dc=(torch.rand(P, 1, 3, generator=g) - 0.5) / 0.28209479177387814,
                                   f_rest=torch.zeros(P, 15, 3), opacity=torch.full((P, 1), 3.0),      # sigmoid -> 0.95
                                   scale=torch.full((P, 3), math.log(0.008)), rot=torch.tensor([[1.0, 0, 0, 0]]).repeat(P, 1))
     formats.export_gaussian_ply(os.path.join(out, "point_cloud.ply"), cloud)
@@ -44,9 +54,11 @@ def write_inputs(out):
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else "extract_mesh_out"
+    args = [a for a in sys.argv[1:] if a != "--clean"]
+    clean = "--clean" in sys.argv[1:]
+    out = args[0] if args else "extract_mesh_out"
     os.makedirs(out, exist_ok=True)
-    write_inputs(out)
+    write_inputs(out, floater=clean)
     dev = torch.device("cuda:0")
     pcd = formats.load_gaussian_ply(os.path.join(out, "point_cloud.ply"), device=dev)
     cameras = formats.load_cameras_json(os.path.join(out, "cameras.json"))
@@ -72,6 +84,9 @@ def main():
         # pixel patches whose rays share voxels in both image directions (same volume, 2.3x faster than a flat list)
         pts = pp.depth_to_points(depth, K, cam.viewmatrix.t().contiguous(), "world")
         volume.integrate(pts, cam.campos)                                           # :115, points never leave the GPU
+    if clean:
+        clean_mesh(out, volume, len(cameras), t0)
+        return
     vertices, faces = volume.extract_triangle_mesh(min_weight=5)                    # :145
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -82,6 +97,21 @@ def main():
     r = np.linalg.norm(vertices, axis=1)
     print(f"{len(cameras)} views rendered, fused and meshed in {dt * 1e3:.0f} ms: {len(vertices)} vertices, {len(faces)} triangles, "
           f"radius {r.min():.3f} .. {r.max():.3f} (shell at 0.92 .. 1.08)")
+
+
+def clean_mesh(out, volume, num_views, t0):
+    from gaustudio_amd import mesh_clean
+    vertices, faces = volume.extract_triangle_mesh_device(min_weight=5)             # :145, the mesh stays in HBM
+    _, n_triangles, area = mesh_clean.cluster_connected_triangles(faces, vertices=vertices)              # :158-160
+    v2, f2, removed = mesh_clean.remove_small_components(vertices, faces, ratio_threshold=0.5)          # :152-182
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    formats.write_ply_mesh(os.path.join(out, "fused_mesh.ply"), v2, f2)                                # :186
+    order = torch.argsort(n_triangles, descending=True)[:5].cpu()
+    top = ", ".join(f"{int(n_triangles[i])} triangles / area {float(area[i]):.4f}" for i in order)
+    print(f"{num_views} views rendered, fused, meshed and cleaned in {dt * 1e3:.0f} ms: {faces.shape[0]} triangles in "
+          f"{n_triangles.numel()} clusters ({mesh_clean.last_rounds} rounds; largest: {top}); removed {removed} triangles and "
+          f"{vertices.shape[0] - v2.shape[0]} vertices -> fused_mesh.ply with {v2.shape[0]} vertices, {f2.shape[0]} triangles")
 
 
 if __name__ == "__main__":

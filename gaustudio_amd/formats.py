@@ -144,6 +144,85 @@ def write_ply_vertices(path, vertices: np.ndarray, comments: Sequence[str] = ())
         f.write(np.ascontiguousarray(vertices.astype(np.dtype(disk))).tobytes())
 
 
+def write_ply_mesh(path, vertices, faces, comments: Sequence[str] = ()):
+    """A triangle mesh as binary_little_endian PLY: `element vertex` with float32 x y z, `element face` with
+    `property list uchar int vertex_indices` (three per face).  vertices [V,3], faces [F,3] (numpy arrays or tensors).
+    The container format only: parity with the writers of trimesh / Open3D (comment lines, property order of richer meshes) is
+    unpinned, as for plyfile."""
+    v = np.ascontiguousarray(np.asarray(vertices.detach().cpu() if torch.is_tensor(vertices) else vertices, dtype="<f4"))
+    t = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise PlyFormatError(f"vertices must have shape [V, 3], got {list(v.shape)}")
+    if t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in "iu":
+        raise PlyFormatError(f"faces must be an integer array of shape [F, 3], got {t.dtype} {list(t.shape)}")
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= max(len(v), 1) or int(t.max()) >= 2 ** 31):
+        raise PlyFormatError("face indices out of range")
+    lines = ["ply", "format binary_little_endian 1.0"] + [f"comment {c}" for c in comments]
+    lines += [f"element vertex {len(v)}", "property float x", "property float y", "property float z",
+              f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    rec = np.empty(len(t), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    rec["n"] = 3
+    rec["i"] = t
+    with open(path, "wb") as f:
+        f.write(("\n".join(lines) + "\n").encode("ascii"))
+        f.write(v.tobytes())
+        f.write(rec.tobytes())
+
+
+def _face_list_types(path):
+    """(count type, index type) numpy codes of the face element's list property (the header reader keeps only its name)."""
+    with open(path, "rb") as f:
+        element = None
+        for line in f:
+            tok = line.decode("ascii", errors="replace").split()
+            if tok[:1] == ["end_header"]:
+                break
+            if tok[:1] == ["element"]:
+                element = tok[1]
+            elif element == "face" and tok[:2] == ["property", "list"]:
+                if tok[2] not in _PLY_SCALARS or tok[3] not in _PLY_SCALARS:
+                    raise PlyFormatError(f"unknown PLY list types in {line!r}")
+                return _PLY_SCALARS[tok[2]], _PLY_SCALARS[tok[3]]
+    raise PlyFormatError("the face element has no list property")
+
+
+def read_ply_mesh(path):
+    """(vertices [V,3] float32, faces [F,3] int32) of a binary PLY triangle mesh: the x, y, z of `element vertex` and the one
+    list property of `element face` (any integer count / index types; every face must have three indices).  Other vertex
+    properties are skipped; elements must come in the order vertex, face."""
+    with open(path, "rb") as f:
+        fmt, elements = _read_header(f)
+        if fmt == "ascii":
+            raise PlyFormatError("read_ply_mesh reads binary PLY files")
+        order = {"binary_little_endian": "<", "binary_big_endian": ">"}[fmt]
+        names = [e[0] for e in elements]
+        if names[:2] != ["vertex", "face"]:
+            raise PlyFormatError(f"expected the elements vertex, face; got {names}")
+        (_, nv, vprops), (_, nf, fprops) = elements[:2]
+        if any(code is None for _, code in vprops):
+            raise PlyFormatError("list properties on the vertex element are not supported")
+        if len(fprops) != 1 or fprops[0][1] is not None:
+            raise PlyFormatError("the face element must hold exactly one list property")
+        vdt = np.dtype([(n, order + code) for n, code in vprops])
+        raw = f.read(nv * vdt.itemsize)
+        if len(raw) != nv * vdt.itemsize:
+            raise PlyFormatError("truncated vertex data")
+        vs = np.frombuffer(raw, dtype=vdt, count=nv)
+        for n in "xyz":
+            if n not in (vdt.names or ()):
+                raise PlyFormatError(f"the vertex element has no property {n!r}")
+        vertices = np.stack([vs["x"], vs["y"], vs["z"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+        ct, it = _face_list_types(path)
+        fdt = np.dtype([("n", order + ct), ("i", order + it, (3,))])
+        raw = f.read(nf * fdt.itemsize)
+        if len(raw) != nf * fdt.itemsize:
+            raise PlyFormatError("truncated face data (or a face that is not a triangle)")
+        fs = np.frombuffer(raw, dtype=fdt, count=nf)
+        if nf and not (fs["n"] == 3).all():
+            raise PlyFormatError("read_ply_mesh reads triangle meshes only")
+        return vertices, fs["i"].astype(np.int32).reshape(-1, 3)
+
+
 DEFAULT_ATTRIBUTES = ("xyz", "f_dc", "f_rest", "opacity", "scale", "rot")
 
 

@@ -123,7 +123,16 @@ class TSDFVolume:
         v, t = self.extract_triangle_mesh_device(fill_holes, min_weight)
         return v.double().cpu().numpy(), t.cpu().numpy()
 
-    def extract_triangle_mesh_device(self, fill_holes=True, min_weight=0.5):
+    def extract_triangle_mesh_device(self, fill_holes=True, min_weight=0.5, clean_ratio=None):
+        """(vertices [nv,3] float32, triangles [nt,3] int32) as device tensors.  clean_ratio (a float; extract_mesh.py --clean
+        uses 0.5): mesh_clean.remove_small_components(vertices, triangles, clean_ratio) is applied before returning."""
+        vertices, triangles = self._extract_triangle_mesh_device(fill_holes, min_weight)
+        if clean_ratio is not None:
+            from .mesh_clean import remove_small_components
+            vertices, triangles, _ = remove_small_components(vertices, triangles, float(clean_ratio))
+        return vertices, triangles
+
+    def _extract_triangle_mesh_device(self, fill_holes, min_weight):
         slots, _ = self.occupied_blocks()
         n = slots.shape[0]
         dev = self.device

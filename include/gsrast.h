@@ -572,6 +572,40 @@ int gsr_mesh_vertex_normals(gsr_alloc_fn workspace_alloc, void* workspace_ctx, c
 int gsr_mesh_visible_faces(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const int* pix_to_face, int num_pixels, int num_faces,
                            unsigned char* visible, void* stream);
 
+/* ---- mesh cleaning: the --clean stage of gaustudio/scripts/extract_mesh.py:149-186 (Open3D's cluster_connected_triangles,
+ * the per-cluster areas, remove_triangles_by_mask + remove_unreferenced_vertices) for a mesh that stays in HBM.  Additive to
+ * ABI 6, in the style of gsr_knn / gsr_mesh_*: inputs and outputs are caller-owned device memory, scratch comes from the
+ * gsr_alloc_fn callback (called once per call), `stream` is the HIP stream of every launch; each entry reads counts and an
+ * error flag back, so it waits on `stream` (gsr_mesh_cluster_triangles: once per batch of four rounds).  Deterministic: integer
+ * atomics only, no float atomics; bit-identical from run to run.  Contract: INTEGRATION.md s16; design: gsr_mesh_clean.hip,
+ * DESIGN.md s13. ---- */
+
+/* faces[num_faces,3] i32 with indices in [0, num_verts), 3 num_faces < 2^31.  Two triangles are adjacent when they share an
+ * undirected edge {min(a,b), max(a,b)} (a shared vertex alone does not connect; an edge with more than two triangles connects
+ * all of them; a triangle that repeats an index behaves as its three literal edges say).  Writes triangle_clusters[num_faces]
+ * (the cluster of each triangle) and cluster_n_triangles[C] (the buffer must hold num_faces entries); clusters are numbered in
+ * ascending order of their lowest triangle index.  *rounds (HOST, may be NULL) receives the number of hook-and-jump rounds
+ * run until one changed nothing (O(log num_faces), independent of the mesh's diameter).  Returns C >= 0, or GSR_ERR_ARG for a
+ * face index outside [0, num_verts) (nothing is written then). */
+int gsr_mesh_cluster_triangles(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const int* faces, int num_faces, int num_verts,
+                               int* triangle_clusters, int* cluster_n_triangles, int* rounds, void* stream);
+
+/* cluster_area[num_clusters] f64 = per cluster the sum of 0.5 |(v1 - v0) x (v2 - v0)| (fp64 from the f32 verts, Open3D
+ * GetTriangleArea) over its triangles, in a fixed order: the triangles in ascending order in pieces of 1024, each piece summed
+ * by 64 strided partial sums and a fixed tree, the pieces added in order.  GSR_ERR_ARG for a cluster index outside
+ * [0, num_clusters) or a face index outside [0, num_verts). */
+int gsr_mesh_cluster_area(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* verts, int num_verts, const int* faces,
+                          int num_faces, const int* triangle_clusters, int num_clusters, double* cluster_area, void* stream);
+
+/* remove_triangles_by_mask + remove_unreferenced_vertices: the faces with keep[f] != 0 (u8) in their original order, the
+ * vertices one of them references in their original order, the faces rewritten with the new vertex indices.  out_faces and
+ * face_index (new face -> old face) must hold num_faces faces / entries, out_verts and vertex_index (new vertex -> old
+ * vertex) num_verts; verts / out_verts may both be NULL (indices only).  Returns the number of kept faces and stores the
+ * number of kept vertices in *num_verts_out (HOST); GSR_ERR_ARG for a face index outside [0, num_verts) (nothing is written). */
+int gsr_mesh_compact(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* verts, int num_verts, const int* faces,
+                     int num_faces, const unsigned char* keep, float* out_verts, int* out_faces, int* vertex_index, int* face_index,
+                     int* num_verts_out, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

@@ -6,9 +6,12 @@ stage on the MI355X:
         -> depth_to_normals -> world normals -> view_records -> NormalFusion -> clean_point_cloud -> fused.ply
 
 Runs on the synthetic shell of extract_mesh_synthetic.py, so it needs no dataset:
-    python examples/extract_pcd_synthetic.py [out_dir]
-Meshing (SAP / Poisson / NKSR) is not part of this example.
+    python examples/extract_pcd_synthetic.py [out_dir] [--meshing {sap,None}] [--dpsr_res R]
+--meshing sap (the reference's default mesher; here the default is None, the behaviour before the option existed) runs
+gaustudio_amd.sap.mesh_sap on the cleaned cloud and writes fused_mesh.ply.  The other meshers of the script (NKSR, Open3D
+Poisson, pymeshlab) are third-party packages and not part of this example.
 """
+import argparse
 import os
 import sys
 import time
@@ -23,7 +26,12 @@ from gaustudio_amd import GaussianRasterizationSettings, GaussianRasterizer, for
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else "extract_pcd_out"
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("out", nargs="?", default="extract_pcd_out")
+    ap.add_argument("--meshing", choices=["sap", "None"], default="None")
+    ap.add_argument("--dpsr_res", type=int, default=256)
+    args = ap.parse_args()
+    out = args.out
     os.makedirs(out, exist_ok=True)
     write_inputs(out)
     dev = torch.device("cuda:0")
@@ -82,6 +90,13 @@ def main():
     outward = float(((n * p).sum(axis=1) > 0).mean()) if len(p) else 0.0
     print(f"{len(cameras)} views, {fusion.num_records} records -> {len(unique_ids)} fused points, {len(p)} after cleaning; "
           f"{100 * outward:.1f} % of the normals point outward")
+    if args.meshing == "sap":
+        from gaustudio_amd import sap
+        t0 = tick()
+        vertices, faces = sap.mesh_sap(points[kept].contiguous(), fused[kept].contiguous(), dpsr_res=args.dpsr_res)
+        times["meshing"] = tick() - t0
+        formats.write_ply_mesh(os.path.join(out, "fused_mesh.ply"), vertices, faces)
+        print(f"sap meshing at {args.dpsr_res}^3: {len(vertices)} vertices, {len(faces)} faces -> fused_mesh.ply")
     print("stage times (ms): " + ", ".join(f"{k} {1e3 * t:.1f}" for k, t in times.items()))
 
 

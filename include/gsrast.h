@@ -606,6 +606,60 @@ int gsr_mesh_compact(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const fl
                      int num_faces, const unsigned char* keep, float* out_verts, int* out_faces, int* vertex_index, int* face_index,
                      int* num_verts_out, void* stream);
 
+/* ---- Shape-as-Points meshing: what gs-extract-pcd --meshing sap runs after the point cloud is cleaned
+ * (gaustudio/models/sap.py, gaustudio/utils/graphics_utils.py:19-333: point_rasterize, the spectral solve of DPSR.forward,
+ * grid_interp and its normalisation; a dense marching cubes in place of the CPU round trip through skimage).  Additive to
+ * ABI 6, in the style of gsr_knn / gsr_mesh_*: inputs and outputs are caller-owned device memory, scratch comes from the
+ * gsr_alloc_fn callback (called once per call), `stream` is the HIP stream of every launch; the entries that say so read a
+ * flag or two counts back and wait on `stream` once.  Forward only.  Deterministic: no float atomics, bit-identical from run
+ * to run.  Grids are dense, row-major [r0, r1, r2] f32 with every size >= 2 and r0 r1 r2 < 2^30.  The two FFTs between the
+ * stages are the caller's.  Contract: INTEGRATION.md s17; design: gsr_psr.hip, DESIGN.md s14. ---- */
+#define GSR_PSR_MAX_CHANNELS 4
+
+/* point_rasterize (:157-217): points[num_points,3] f32 in [0, 1), values[num_points,channels] f32, 1 <= channels <= 4.
+ * Per axis, in fp32: cubesize = 1 / size, ind0 = floor(p / cubesize), ind1 = fmod(ceil(p / cubesize), size) (periodic; a
+ * coordinate exactly on a node has ind1 == ind0), the weight of node ind0 is |p - (ind0 + 1) cubesize| / cubesize and that of
+ * ind1 |p - ind0 cubesize| / cubesize; a corner's weight is (wx wy) wz and its term w * value, all fp32.  grid[channels,r0,r1,r2]
+ * receives per node the fp64 sum of the terms that land on it (cells in a fixed order, points in ascending index, corners
+ * ascending), rounded to fp32 once; weighted != 0 divides it (fp32) by the number of (point, corner) pairs on the node,
+ * zero-weight pairs included, 0 replaced by 1.  counts[r0,r1,r2] i32 (NULL = not wanted) receives that number.  Waits on
+ * `stream` once.  GSR_ERR_ARG for a coordinate that is not finite or outside [0, 1) (nothing is written then). */
+int gsr_psr_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, const float* values,
+                      int channels, int r0, int r1, int r2, int weighted, float* grid, int* counts, void* stream);
+
+/* The spectral Poisson solve of DPSR.forward (:305-316) in one pass: spectrum = rfftn of the rasterized normals,
+ * [3, r0, r1, r2/2+1] complex64 (interleaved re, im); phi[r0, r1, r2/2+1] complex64.  Per element, with the integer
+ * frequencies k of np.fft.fftfreq / rfftfreq: G = (float)exp(-0.5 (sig 2 |k| / r0)^2) in fp64; then in fp32 N_d = N_d G,
+ * w_d = (k_d 2) pi, DivN = sum_d (Im N_d w_d, -Re N_d w_d), Lap = -sum_d w_d^2, phi = DivN / (Lap + 1e-6); phi[0,0,0] = 0. */
+int gsr_psr_spectral(const float* spectrum, int r0, int r1, int r2, double sig, float* phi, void* stream);
+
+/* grid_interp (:69-112) of grid[r0,r1,r2] at points[num_points,3] (the index and weight arithmetic of gsr_psr_rasterize):
+ * samples[i] = the 8 terms grid[corner] * w (fp32) added in fp64 in the reference's corner order, rounded once.  mean[1]
+ * (f64, device, NULL = not wanted) = the fp64 sum of the samples in a fixed order (per 256 points a fixed tree, then the
+ * partial sums in a fixed tree) / num_points.  Waits on `stream` once.  GSR_ERR_ARG for a bad coordinate as above. */
+int gsr_psr_interp(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grid, int r0, int r1, int r2, const float* points,
+                   int num_points, float* samples, double* mean, void* stream);
+
+/* The tail of DPSR.forward (:323-332) and the tanh of ShapeAsPoints.generate_mesh in one stream over `count` values, fp32:
+ * v = in - (float)mean[0] when mean (f64[1], device) is given; then with scale != 0 v = -v / |v[0]| * 0.5, v[0] the first
+ * value after the shift; then with apply_tanh != 0 v = tanh(v).  grid_out may be grid_in.  params: f32[2] device scratch. */
+int gsr_psr_normalize(const float* grid_in, float* grid_out, long long count, const double* mean, int scale, int apply_tanh,
+                      float* params, void* stream);
+
+/* Dense indexed marching cubes over the (r0-1)(r1-1)(r2-1) cubes of grid[r0,r1,r2] (not periodic) with gsr_mc_tables.h: a
+ * corner is inside iff value < level, triangle normals point towards increasing value.  Every edge between two nodes that
+ * crosses the level carries one vertex, owned by the edge's lower node; a vertex lies at index + (level - a) / (b - a) (fp32,
+ * a the owner's value) along its axis, in index units.  Vertices are ordered by (owner node linear index, axis), triangles by
+ * (linear index of the cube's lower node, table order).  gsr_psr_mc_classify fills node_info[r0 r1 r2] (u32) and the two
+ * exclusive scans vertex_offset / triangle_offset [r0 r1 r2 + 1] (i32), stores the counts in *num_vertices / *num_triangles
+ * (HOST) and waits on `stream` once; gsr_psr_mc_emit writes vertices[num_vertices,3] f32 and faces[num_triangles,3] i32
+ * (either may be NULL). */
+int gsr_psr_mc_classify(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grid, int r0, int r1, int r2, float level,
+                        uint32_t* node_info, int* vertex_offset, int* triangle_offset, int* num_vertices, int* num_triangles,
+                        void* stream);
+int gsr_psr_mc_emit(const float* grid, int r0, int r1, int r2, float level, const uint32_t* node_info, const int* vertex_offset,
+                    const int* triangle_offset, float* vertices, int* faces, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

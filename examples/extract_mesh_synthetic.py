@@ -5,11 +5,15 @@
                                  ->  TSDFVolume.integrate                         ->  extract_triangle_mesh -> PLY
 
 Runs on a synthetic shell of Gaussians written to / read back from the reference's on-disk formats, so it needs no
-dataset:   python examples/extract_mesh_synthetic.py [out_dir] [--clean]
+dataset:   python examples/extract_mesh_synthetic.py [out_dir] [--clean] [--fusion rgbd]
 
 --clean (extract_mesh.py:149-186): the scene gets a small detached blob of Gaussians, the mesh is clustered into connected
 components and the clusters with at most half the triangles of the largest one are removed, all on the device
 (gaustudio_amd.mesh_clean); the result is written as fused_mesh.ply.
+
+--fusion rgbd: every view's rendered RGB goes into a ColorTSDFVolume together with its median depth (voxel-projective fusion
+with a running colour average, gaustudio_amd.tsdf_rgbd) instead of the depth points into a TSDFVolume; the mesh is cleaned,
+written as a COLOURED fused_mesh.ply and rendered back with mesh_raster, the vertex colours as the interpolated attribute.
 """
 import json
 import math
@@ -53,9 +57,61 @@ def write_inputs(out, floater=False):
         json.dump(cams, fjson)
 
 
+def render_rgbd(cam, act, dev):
+    """One view as an RGB-D frame: (median depth [H,W] with 0 where the opacity is below 0.5, RGB [3,H,W] in [0,1],
+    (fx, fy, cx, cy), world-to-camera 4x4)."""
+    rs = GaussianRasterizationSettings(cam.height, cam.width, cam.tanfovx, cam.tanfovy, torch.zeros(3), 1.0,
+                                       cam.viewmatrix.to(dev), cam.projmatrix.to(dev), 0, cam.campos.to(dev), False, False)
+    with torch.no_grad():
+        color, _, _, median, opacity = GaussianRasterizer(rs)(means3D=act["means3D"], means2D=torch.zeros_like(act["means3D"]),
+                                                               opacities=act["opacities"], shs=act["shs"], scales=act["scales"],
+                                                               rotations=act["rotations"])
+    depth = median[0].clone()
+    depth[opacity[0] < 0.5] = 0                                                     # extract_mesh.py:104-107
+    f = cam.width / (2 * cam.tanfovx)
+    return depth, color.clamp(0.0, 1.0).contiguous(), (f, f, cam.width / 2, cam.height / 2), cam.viewmatrix.t().numpy().astype(np.float64)
+
+
+def fuse_rgbd_mesh(out, act, cameras, dev):
+    from gaustudio_amd import ColorTSDFVolume
+    from gaustudio_amd.mesh_raster import MeshRasterizer
+    volume = ColorTSDFVolume(voxel_length=0.01, sdf_trunc=0.04, capacity_blocks=1 << 16)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for rec in cameras:
+        depth, rgb, K, E = render_rgbd(rec.cam, act, dev)
+        volume.integrate(depth, rgb, K, E, depth_trunc=10.0)                         # images never leave the GPU
+    v, f, c, n = volume.extract_triangle_mesh_device(min_weight=5, clean_ratio=0.5, with_normals=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    formats.write_ply_mesh(os.path.join(out, "fused_mesh.ply"), v, f, vertex_colors=c, vertex_normals=n)
+    # render the coloured mesh back into the first camera: the vertex colours are the interpolated attribute
+    cam = cameras[0].cam
+    depth, rgb, K, E = render_rgbd(cam, act, dev)
+    Kmat = np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1]])
+    mr = MeshRasterizer(v, f)
+    frags = mr.rasterize(Kmat, E, cam.height, cam.width)
+    img = mr.interpolate(frags, c)
+    both = (frags.pix_to_face >= 0) & (depth > 0)
+    err = (img[both] - rgb.permute(1, 2, 0)[both]).abs().mean().item() if bool(both.any()) else float("nan")
+    np.save(os.path.join(out, "fused_mesh_render.npy"), (img.clamp(0, 1) * 255 + 0.5).to(torch.uint8).cpu().numpy())
+    r = v.norm(dim=1)
+    print(f"{len(cameras)} views rendered, RGB-D fused, meshed and cleaned in {dt * 1e3:.0f} ms: coloured fused_mesh.ply with "
+          f"{v.shape[0]} vertices, {f.shape[0]} triangles, radius {r.min():.3f} .. {r.max():.3f} (shell at 0.92 .. 1.08); "
+          f"rendered back into view 0: mean |colour - rendered RGB| = {err:.3f} over {int(both.sum())} pixels")
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--clean"]
-    clean = "--clean" in sys.argv[1:]
+    argv = sys.argv[1:]
+    fusion = "points"
+    if "--fusion" in argv:
+        i = argv.index("--fusion")
+        fusion = argv[i + 1]
+        del argv[i:i + 2]
+        if fusion not in ("points", "rgbd"):
+            sys.exit("--fusion takes points or rgbd")
+    args = [a for a in argv if a != "--clean"]
+    clean = "--clean" in argv
     out = args[0] if args else "extract_mesh_out"
     os.makedirs(out, exist_ok=True)
     write_inputs(out, floater=clean)
@@ -63,6 +119,9 @@ def main():
     pcd = formats.load_gaussian_ply(os.path.join(out, "point_cloud.ply"), device=dev)
     cameras = formats.load_cameras_json(os.path.join(out, "cameras.json"))
     act = pcd.activated()
+    if fusion == "rgbd":
+        fuse_rgbd_mesh(out, act, cameras, dev)
+        return
     volume = TSDFVolume(voxel_size=0.01, sdf_trunc=0.04, space_carving=False, capacity_blocks=1 << 18)   # extract_mesh.py:86
     torch.cuda.synchronize()
     t0 = time.perf_counter()

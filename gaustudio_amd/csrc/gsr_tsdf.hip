@@ -24,12 +24,12 @@
 #include <stdint.h>
 
 #include "../../include/gsrast.h"
+#include "gsr_internal.h"
 #include "gsr_mc_tables.h"
 
 namespace {
 
-constexpr uint64_t EMPTY = ~0ull;
-constexpr int BLOCK_VOX = 512;
+constexpr int BLOCK_VOX = gsr::TSDF_BLOCK_VOX;
 constexpr float QSCALE = 32768.0f;   // 2^15: 2^24 observations x 2^15 fit the 40-bit signed sum field
 
 __device__ __constant__ uint8_t d_ntris[256];
@@ -40,45 +40,11 @@ __device__ __constant__ int d_corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {
 __device__ __constant__ uint8_t d_edge_owner[12] = {0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3};
 __device__ __constant__ uint8_t d_edge_axis[12] = {0, 1, 0, 1, 0, 1, 0, 1, 2, 2, 2, 2};
 
-__host__ __device__ __forceinline__ uint64_t block_key(int bx, int by, int bz)
-{
-	const uint64_t B = 1u << 20;
-	return ((uint64_t)(bx + (int)B) << 42) | ((uint64_t)(by + (int)B) << 21) | (uint64_t)(bz + (int)B);
-}
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-	x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-	x ^= x >> 27; x *= 0x94d049bb133111ebull;
-	x ^= x >> 31;
-	return x;
-}
-
-// returns the slot of `key`, inserting it if absent; -1 when the table is full (probe limit)
-__device__ int64_t find_or_insert(unsigned long long* keys, uint64_t mask, uint64_t key)
-{
-	uint64_t slot = mix64(key) & mask;
-	for (uint64_t probe = 0; probe <= mask; probe++) {
-		unsigned long long k = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
-		if (k == key) return (int64_t)slot;
-		if (k == EMPTY) {
-			const unsigned long long old = atomicCAS(&keys[slot], (unsigned long long)EMPTY, (unsigned long long)key);
-			if (old == EMPTY || old == key) return (int64_t)slot;
-		}
-		slot = (slot + 1) & mask;
-	}
-	return -1;
-}
-__device__ int64_t find_slot(const unsigned long long* keys, uint64_t mask, uint64_t key)
-{
-	uint64_t slot = mix64(key) & mask;
-	for (uint64_t probe = 0; probe <= mask; probe++) {
-		const unsigned long long k = keys[slot];
-		if (k == key) return (int64_t)slot;
-		if (k == EMPTY) return -1;
-		slot = (slot + 1) & mask;
-	}
-	return -1;
-}
+// block keys and the hash probes: gsr_internal.h (shared with gsr_tsdf_rgbd.hip)
+using gsr::tsdf_block_key;
+using gsr::tsdf_decode_key;
+using gsr::tsdf_find_or_insert;
+using gsr::tsdf_find_slot;
 
 // OpenVDB math::MinIndex: index of the smallest component with its tie-breaking table
 __device__ __forceinline__ int min_index(float a, float b, float c)
@@ -97,7 +63,7 @@ __device__ __forceinline__ bool tsdf_commit(unsigned long long* __restrict__ key
 {
 	const int bxk = vx >> 3, byk = vy >> 3, bzk = vz >> 3;
 	if (bxk != cbx || byk != cby || bzk != cbz) {
-		cached_slot = find_or_insert(keys, mask, block_key(bxk, byk, bzk));
+		cached_slot = tsdf_find_or_insert(keys, mask, tsdf_block_key(bxk, byk, bzk));
 		cbx = bxk; cby = byk; cbz = bzk;
 	}
 	if (cached_slot < 0) { atomicOr(&status[0], 1u); return false; }   // table full
@@ -280,14 +246,6 @@ __global__ __launch_bounds__(512) void tsdf_export_kernel(const unsigned long lo
 
 // ---- marching cubes over the occupied blocks (blocks[] = hash slots in a caller-chosen, deterministic order) ----
 // s_nb[8]: hash slots of the 2x2x2 blocks starting at the workgroup's block (-1 = absent), index dz*4+dy*2+dx
-__device__ __forceinline__ void decode_key(uint64_t key, int& bx, int& by, int& bz)
-{
-	const int B = 1 << 20;
-	bx = (int)((key >> 42) & 0x1fffff) - B;
-	by = (int)((key >> 21) & 0x1fffff) - B;
-	bz = (int)(key & 0x1fffff) - B;
-}
-
 // value of the voxel at local coordinates (lx,ly,lz) in [0,8] of the 2x2x2 block neighbourhood; false = block absent
 __device__ __forceinline__ bool fetch(const unsigned long long* __restrict__ vox, const int64_t* nb, int lx, int ly, int lz,
                                       float sdf_trunc, float& f, uint32_t& c)
@@ -328,9 +286,9 @@ __global__ __launch_bounds__(512) void mc_classify_kernel(const unsigned long lo
 	const uint32_t slot = blocks[blockIdx.x];
 	if (threadIdx.x < 8) {
 		int bx, by, bz;
-		decode_key(keys[slot], bx, by, bz);
+		tsdf_decode_key(keys[slot], bx, by, bz);
 		s_nb[threadIdx.x] = threadIdx.x == 0 ? (int64_t)slot
-		                                     : find_slot(keys, mask, block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
+		                                     : tsdf_find_slot(keys, mask, tsdf_block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
 	}
 	__syncthreads();
 	const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
@@ -397,10 +355,10 @@ __global__ __launch_bounds__(512) void mc_vertices_kernel(const unsigned long lo
 	const uint32_t slot = blocks[blockIdx.x];
 	if (threadIdx.x < 8) {
 		int bx, by, bz;
-		decode_key(keys[slot], bx, by, bz);
+		tsdf_decode_key(keys[slot], bx, by, bz);
 		if (threadIdx.x == 0) { s_b[0] = bx; s_b[1] = by; s_b[2] = bz; }
 		s_nb[threadIdx.x] = threadIdx.x == 0 ? (int64_t)slot
-		                                     : find_slot(keys, mask, block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
+		                                     : tsdf_find_slot(keys, mask, tsdf_block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
 	}
 	__syncthreads();
 	const size_t i = (size_t)blockIdx.x * BLOCK_VOX + threadIdx.x;
@@ -442,9 +400,9 @@ __global__ __launch_bounds__(512) void mc_triangles_kernel(const unsigned long l
 	const uint32_t slot = blocks[blockIdx.x];
 	if (threadIdx.x < 8) {
 		int bx, by, bz;
-		decode_key(keys[slot], bx, by, bz);
+		tsdf_decode_key(keys[slot], bx, by, bz);
 		s_nb[threadIdx.x] = threadIdx.x == 0 ? (int64_t)slot
-		                                     : find_slot(keys, mask, block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
+		                                     : tsdf_find_slot(keys, mask, tsdf_block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
 	}
 	__syncthreads();
 	const size_t i = (size_t)blockIdx.x * BLOCK_VOX + threadIdx.x;
@@ -482,6 +440,29 @@ int load_tables()
 bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
 
 }  // namespace
+
+namespace gsr {
+
+int launch_tsdf_mc_count(int num_blocks, const uint8_t* cases, const uint32_t* flags, uint32_t* block_nv, uint32_t* block_nt, hipStream_t s)
+{
+	const int rc = load_tables();
+	if (rc != GSR_OK) return rc;
+	hipLaunchKernelGGL(mc_count_kernel, dim3(num_blocks), dim3(512), 0, s, cases, flags, block_nv, block_nt);
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int launch_tsdf_mc_triangles(const uint64_t* keys, uint64_t capacity, const uint32_t* blocks, int num_blocks, const uint32_t* cidx,
+                             const uint8_t* cases, const uint32_t* flags, const uint32_t* vbase, const uint32_t* block_toff,
+                             int* triangles, hipStream_t s)
+{
+	const int rc = load_tables();
+	if (rc != GSR_OK) return rc;
+	hipLaunchKernelGGL(mc_triangles_kernel, dim3(num_blocks), dim3(512), 0, s, reinterpret_cast<const unsigned long long*>(keys),
+	                   capacity - 1, blocks, cidx, cases, flags, vbase, block_toff, triangles);
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+}  // namespace gsr
 
 extern "C" {
 

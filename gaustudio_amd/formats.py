@@ -144,28 +144,54 @@ def write_ply_vertices(path, vertices: np.ndarray, comments: Sequence[str] = ())
         f.write(np.ascontiguousarray(vertices.astype(np.dtype(disk))).tobytes())
 
 
-def write_ply_mesh(path, vertices, faces, comments: Sequence[str] = ()):
+def _np(a):
+    return np.asarray(a.detach().cpu() if torch.is_tensor(a) else a)
+
+
+def write_ply_mesh(path, vertices, faces, comments: Sequence[str] = (), vertex_colors=None, vertex_normals=None):
     """A triangle mesh as binary_little_endian PLY: `element vertex` with float32 x y z, `element face` with
     `property list uchar int vertex_indices` (three per face).  vertices [V,3], faces [F,3] (numpy arrays or tensors).
-    The container format only: parity with the writers of trimesh / Open3D (comment lines, property order of richer meshes) is
-    unpinned, as for plyfile."""
-    v = np.ascontiguousarray(np.asarray(vertices.detach().cpu() if torch.is_tensor(vertices) else vertices, dtype="<f4"))
-    t = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces)
+    vertex_normals [V,3] (optional) follow as float32 nx ny nz; vertex_colors [V,3] (optional; floats in [0,1], quantised as
+    uint8(clip(c, 0, 1) * 255 + 0.5), or uint8 as they are) as uchar red green blue -- the vertex layout Open3D and trimesh
+    write.  The container format only: parity with the writers of trimesh / Open3D (comment lines) is unpinned, as for plyfile."""
+    v = np.ascontiguousarray(np.asarray(_np(vertices), dtype="<f4"))
+    t = _np(faces)
     if v.ndim != 2 or v.shape[1] != 3:
         raise PlyFormatError(f"vertices must have shape [V, 3], got {list(v.shape)}")
     if t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in "iu":
         raise PlyFormatError(f"faces must be an integer array of shape [F, 3], got {t.dtype} {list(t.shape)}")
     if t.size and (int(t.min()) < 0 or int(t.max()) >= max(len(v), 1) or int(t.max()) >= 2 ** 31):
         raise PlyFormatError("face indices out of range")
+    fields, props = [("xyz", "<f4", (3,))], ["property float x", "property float y", "property float z"]
+    attrs = {}
+    if vertex_normals is not None:
+        n = np.asarray(_np(vertex_normals), dtype="<f4")
+        if n.shape != v.shape:
+            raise PlyFormatError(f"vertex_normals must have shape {list(v.shape)}, got {list(n.shape)}")
+        attrs["n"] = n
+        fields.append(("n", "<f4", (3,)))
+        props += ["property float nx", "property float ny", "property float nz"]
+    if vertex_colors is not None:
+        c = _np(vertex_colors)
+        if c.shape != v.shape:
+            raise PlyFormatError(f"vertex_colors must have shape {list(v.shape)}, got {list(c.shape)}")
+        if c.dtype != np.uint8:
+            c = (np.clip(c.astype(np.float64), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        attrs["c"] = c
+        fields.append(("c", "u1", (3,)))
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
     lines = ["ply", "format binary_little_endian 1.0"] + [f"comment {c}" for c in comments]
-    lines += [f"element vertex {len(v)}", "property float x", "property float y", "property float z",
-              f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    lines += [f"element vertex {len(v)}"] + props + [f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    vrec = np.empty(len(v), dtype=np.dtype(fields))
+    vrec["xyz"] = v
+    for k, a in attrs.items():
+        vrec[k] = a
     rec = np.empty(len(t), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
     rec["n"] = 3
     rec["i"] = t
     with open(path, "wb") as f:
         f.write(("\n".join(lines) + "\n").encode("ascii"))
-        f.write(v.tobytes())
+        f.write(vrec.tobytes())
         f.write(rec.tobytes())
 
 
@@ -186,10 +212,12 @@ def _face_list_types(path):
     raise PlyFormatError("the face element has no list property")
 
 
-def read_ply_mesh(path):
+def read_ply_mesh(path, return_attributes=False):
     """(vertices [V,3] float32, faces [F,3] int32) of a binary PLY triangle mesh: the x, y, z of `element vertex` and the one
     list property of `element face` (any integer count / index types; every face must have three indices).  Other vertex
-    properties are skipped; elements must come in the order vertex, face."""
+    properties are skipped; elements must come in the order vertex, face.  return_attributes: a third value, a dict with
+    "colors" ([V,3] in the file's type, uint8 for uchar red green blue) and "normals" ([V,3] float32: nx ny nz) where the
+    file has them."""
     with open(path, "rb") as f:
         fmt, elements = _read_header(f)
         if fmt == "ascii":
@@ -220,7 +248,16 @@ def read_ply_mesh(path):
         fs = np.frombuffer(raw, dtype=fdt, count=nf)
         if nf and not (fs["n"] == 3).all():
             raise PlyFormatError("read_ply_mesh reads triangle meshes only")
-        return vertices, fs["i"].astype(np.int32).reshape(-1, 3)
+        faces = fs["i"].astype(np.int32).reshape(-1, 3)
+        if not return_attributes:
+            return vertices, faces
+        attrs = {}
+        have = vdt.names or ()
+        if all(n in have for n in ("red", "green", "blue")):
+            attrs["colors"] = np.stack([vs["red"], vs["green"], vs["blue"]], axis=1).astype(vdt["red"].newbyteorder("="))
+        if all(n in have for n in ("nx", "ny", "nz")):
+            attrs["normals"] = np.stack([vs["nx"], vs["ny"], vs["nz"]], axis=1).astype(np.float32)
+        return vertices, faces, attrs
 
 
 DEFAULT_ATTRIBUTES = ("xyz", "f_dc", "f_rest", "opacity", "scale", "rot")

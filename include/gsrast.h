@@ -459,6 +459,45 @@ int gsr_tsdf_mc_emit(const uint64_t* block_keys, uint64_t capacity, const uint64
                      const uint32_t* edge_flags, const uint32_t* block_vertex_offset, const uint32_t* block_triangle_offset,
                      uint32_t* vertex_base, float* vertices, int* triangles, void* stream);
 
+/* ---- Coloured TSDF from posed RGB-D frames: what the `tsdf` initializer does on the CPU
+ * (gaustudio/pipelines/initializers/mesh.py:445-514 -> Open3D ScalableTSDFVolume(color_type=RGB8).integrate /
+ * .extract_triangle_mesh).  Additive to ABI 6.  Voxel-projective: every voxel of every block a frame's depth touches projects
+ * into the depth image and keeps float running averages.  Stateless; the volume is caller-owned device memory --
+ *   block_keys[capacity] u64 and status[1] u32 exactly as above (bit 0: the hash overflowed);
+ *   voxels[capacity * 5 * 512] f32, zero-initialised: per hash slot the planes tsdf (in units of sdf_trunc), weight, r, g, b
+ *       (0..255) of the block's 512 voxels, x fastest;
+ *   slot_stamp[capacity] i32, zero-initialised: the number of the last frame that touched the slot.
+ * Voxel (i,j,k) has its centre at ((i,j,k) + 0.5) voxel_length.  Matrices are rows 0..2 of a rigid 4x4, row-major, HOST.
+ * Semantics, operation by operation: tests/tsdf_rgbd_model.py; contract: INTEGRATION.md s18; design: DESIGN.md s15. ---- */
+
+/* Allocation: for every pixel (u, v) with u % stride == 0 and v % stride == 0 whose cleaned depth d (non-finite, negative
+ * and > depth_trunc count as 0) is > 0, opens every block that intersects the box +-sdf_trunc around
+ * cam_to_world ((u - cx) d / fx, (v - cy) d / fy, d) and stores `frame` (> 0) into slot_stamp of its slot.  intrinsic = {fx, fy,
+ * cx, cy}.  lane_filter != 0: a lane whose box of blocks equals its lane-neighbour's leaves the insertion to it (same
+ * result, fewer hash probes); counters (device, optional) [0] += insertions asked for, [1] += insertions made. */
+int gsr_ctsdf_touch(const float* depth, int width, int height, int stride, const float intrinsic[4], const float cam_to_world[12],
+                    float depth_trunc, float voxel_length, float sdf_trunc, uint64_t* block_keys, uint64_t capacity,
+                    int* slot_stamp, int frame, uint32_t* status, int lane_filter, uint64_t* counters, void* stream);
+/* Integration of one frame into the listed slots (those stamped by gsr_ctsdf_touch for this frame, any order, no slot twice).
+ * color_mode 0: u8 [H,W,3]; 1: f32 [H,W,3] in [0,1]; 2: f32 [3,H,W] in [0,1] (float colour is quantised on load:
+ * uint8(clip(x * 255, 0, 255)), truncating).  No atomics: one thread owns one voxel. */
+int gsr_ctsdf_integrate(const float* depth, const void* color, int color_mode, int width, int height, const float intrinsic[4],
+                        const float world_to_cam[12], float depth_trunc, float voxel_length, float sdf_trunc,
+                        const uint64_t* block_keys, const int* touched_slots, int num_touched, float* voxels, void* stream);
+/* Test / inspection: tsdf[n*512], weight[n*512], color[n*512*3] of the listed slots (x fastest). */
+int gsr_ctsdf_export_blocks(const float* voxels, const uint32_t* block_slots, int num_blocks, float* tsdf, float* weight, float* color,
+                            void* stream);
+/* ExtractTriangleMesh in the two steps of gsr_tsdf_mc_classify / _emit (same block lists, scans, tables and vertex sharing).
+ * A cube is meshed iff all 8 corner voxels have weight > 0 and weight >= min_weight; inside = tsdf < 0.  emit also writes
+ * colors[nv,3] f32 in [0,1]: the linear interpolation of the edge's two voxel colours at the zero crossing. */
+int gsr_ctsdf_mc_classify(const uint64_t* block_keys, uint64_t capacity, const float* voxels, const uint32_t* block_slots, int num_blocks,
+                          const uint32_t* slot_to_block, float min_weight, uint8_t* cases, uint32_t* edge_flags,
+                          uint32_t* block_num_vertices, uint32_t* block_num_triangles, void* stream);
+int gsr_ctsdf_mc_emit(const uint64_t* block_keys, uint64_t capacity, const float* voxels, const uint32_t* block_slots, int num_blocks,
+                      const uint32_t* slot_to_block, float voxel_length, const uint8_t* cases, const uint32_t* edge_flags,
+                      const uint32_t* block_vertex_offset, const uint32_t* block_triangle_offset, uint32_t* vertex_base, float* vertices,
+                      float* colors, int* triangles, void* stream);
+
 /* ---- 2D Gaussian surfels ("2DGS": the operator behind diff_surfel_rasterization) ----
  * Additive to ABI 6.  The same allocator callbacks, stream and gsr_options as gsr_forward_ex (fast_exp is honoured; the binning
  * options do not apply: surfels are binned into the reference's square tile rects).  scales are [P,2], rotations [P,4]

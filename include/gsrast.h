@@ -699,6 +699,38 @@ int gsr_psr_mc_classify(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const
 int gsr_psr_mc_emit(const float* grid, int r0, int r1, int r2, float level, const uint32_t* node_info, const int* vertex_offset,
                     const int* triangle_offset, float* vertices, int* faces, void* stream);
 
+/* ---- visual hull (csrc/gsr_hull.hip): the `VisualHull` initializer's carve, gaustudio/pipelines/initializers/mask.py:38-71 ----
+ * A camera of the carve: m = full_proj_transform as the reference stores it (row-vector convention, row-major [4][4]:
+ * clip_c = ((x m[c] + y m[4+c]) + z m[8+c]) + m[12+c]); the view's packed mask starts at word_offset of mask_words and has
+ * row_stride words per row (bit x & 31 of word x >> 5 is pixel x).  has_mask = 0: every voxel inside the view is kept. */
+typedef struct gsr_hull_camera {
+	float m[16];
+	int32_t width, height;
+	uint32_t word_offset;
+	int32_t row_stride;
+	int32_t has_mask;
+	int32_t reserved[3];
+} gsr_hull_camera;
+
+/* Packs mask[height,width] (dtype 0: one byte per pixel, uint8 or bool; 1: float32; a pixel is set iff its value is nonzero,
+ * NaN included) into bits at mask_words + word_offset: row y starts at word y * row_stride (row_stride >= ceil(width / 32);
+ * the bits of a row's last word beyond `width` are 0, words of a wider stride are not written).  GSR_ERR_ARG unless
+ * word_offset + height * row_stride <= num_words. */
+int gsr_hull_pack_masks(const void* mask, int dtype, int width, int height, uint32_t* mask_words, uint64_t word_offset, int row_stride,
+                        uint64_t num_words, void* stream);
+
+/* Carves the grid [r0,r1,r2] (r0 r1 r2 < 2^31): voxel (i,j,k), flat index (i r1 + j) r2 + k, sits at (axis_x[j], axis_y[i],
+ * axis_z[k]) (np.meshgrid's 'xy' indexing; axis_x has r1, axis_y r0, axis_z r2 entries, device memory).  Per camera, in list
+ * order, Camera.insideView (gaustudio/datasets/__init__.py:268-305): clip = [x,y,z,1] @ m in the order above, ndc = clip.xy /
+ * clip.w, kept iff clip.z > 0, -1 <= ndc.x, ndc.y <= 1 and the mask bit at (min(max(int((ndc.x + 1) * 0.5f * width), 0),
+ * width - 1), likewise y with (1 + ndc.y) and height) is set.  filled[t] (u8) = 1 iff every camera keeps the voxel; *count
+ * (device u32, zeroed by the call) = number of filled voxels; carved_by[t] (i32, may be NULL) = the first camera that carved
+ * the voxel, -1 for a filled one.  cameras_host[num_cameras] (HOST) is validated (GSR_ERR_ARG for a mask region outside
+ * [0, num_words)) and copied to cameras_device on `stream`: keep it alive until the stream has passed the call (the caller reads *count anyway). */
+int gsr_hull_carve(const float* axis_x, const float* axis_y, const float* axis_z, int r0, int r1, int r2,
+                   const gsr_hull_camera* cameras_host, gsr_hull_camera* cameras_device, int num_cameras, const uint32_t* mask_words,
+                   uint64_t num_words, uint8_t* filled, uint32_t* count, int* carved_by, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

@@ -1421,7 +1421,7 @@ int gsr_surfel_backward(const gsr_options* opt, int P, int D, int M, int R, int 
 		                            reinterpret_cast<const uint32_t*>(image_buffer + il.n_contrib),
 		                            reinterpret_cast<const uint32_t*>(image_buffer + il.med_pos),
 		                            reinterpret_cast<const float*>(image_buffer + sl.m1), reinterpret_cast<const float*>(image_buffer + sl.m2),
-		                            reinterpret_cast<const float*>(image_buffer + sl.m0), out_color, out_allmap, dL_dout_color, dL_dout_allmap, rows, ro.fast_exp != 0, s);
+		                            reinterpret_cast<const float*>(image_buffer + sl.m0), cam, dL_dout_color, dL_dout_allmap, rows, ro.fast_exp != 0, s);
 		STAGE_CHECK("surfel_composite_bwd", debug, s);
 	}
 	launch_surfel_preprocess_bwd(P, width, height, means3D, scales, scale_modifier, rotations, radii, cam, recs, goff, rows, dL_dmean2D,

@@ -289,7 +289,7 @@ void launch_surfel_composite_fwd(const ImgLayout& il, int W, int H, const uint2*
 void launch_surfel_composite_bwd(const ImgLayout& il, int W, int H, const uint2* ranges, const uint32_t* point_list, const SurfRec* recs,
                                  const uint4* binfo, const uint32_t* goff, const float* final_T,
                                  const uint32_t* n_contrib, const uint32_t* med_pos, const float* m1, const float* m2, const float* m0,
-                                 const float* out_color, const float* out_allmap, const float* dL_dcolor, const float* dL_dallmap,
+                                 const GsCam* cam, const float* dL_dcolor, const float* dL_dallmap,
                                  float* rows, bool fast_exp, hipStream_t s);
 void launch_surfel_preprocess_bwd(int P, int W, int H, const float* means3D, const float* scales, float scale_modifier,
                                   const float* rotations, const int* radii, const GsCam* cam, const SurfRec* recs,

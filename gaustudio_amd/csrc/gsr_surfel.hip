@@ -318,12 +318,17 @@ void launch_surfel_composite_fwd(const ImgLayout& il, int W, int H, const uint2*
 }
 
 // ------------------------------------------------------------------------------------------------
-// Backward walk, front to back.  For entry i of a pixel (T_i before it, w_i = alpha_i T_i) and an output O = sum w_j f_j (+ T_f bg):
-//   dO/df_i = w_i,   dO/dalpha_i = T_i f_i - (O - sum_{j<=i} w_j f_j) / (1 - alpha_i)
-// with the forward's outputs as O (colour includes T_f bg).  The distortion dist = sum_{j<i} w_i w_j (m_i - m_j)^2 has
+// Backward walk, BACK TO FRONT, from the tile's last contributor to the first entry.  For entry i of a pixel (T_i before it,
+// w_i = alpha_i T_i) and an output O = sum w_j f_j (+ T_f bg):
+//   dO/df_i = w_i,   dO/dalpha_i = T_i (f_i - R_{i+1}),   R_i = alpha_i f_i + (1 - alpha_i) R_{i+1},   R_{last+1} = bg (colour) or 0
+// R_{i+1} is what lies behind entry i, per unit of the transmittance that reaches it: a convex combination, accumulated
+// directly.  (Formed as the forward's total minus the running prefix -- two O(1) numbers that carry the rounding of every
+// addition -- the remainder loses its relative accuracy as T_i falls towards 1e-4: an absolute error of ~1e-6 on the dL/dalpha
+// of entries deep in a list of a thousand, tests/test_gpu_surfel_edges.py test_long_lists.)  T_i = T_{i+1} / (1 - alpha_i)
+// from the forward's final T.  The distortion dist = sum_{j<i} w_i w_j (m_i - m_j)^2 has
 //   g_i = ddist/dw_i = m_i^2 A_f + M2_f - 2 m_i M1_f,   ddist/dm_i = 2 w_i (m_i A_f - M1_f),   sum_j w_j g_j = 2 dist
 // (A_f = 1 - T_f, M1_f, M2_f: the pixel's final values, kept by the forward, moments of m - mref).  Every decision is the forward's (surf_eval),
-// the walk ends at the forward's last contributor.  Per entry the 16 partials are summed over the wave (butterfly) and then
+// the walk starts at the forward's last contributor.  Per entry the 16 partials are summed over the wave (butterfly) and then
 // over the four waves in a fixed order: the row is bit-identical from run to run.
 #define SURF_CHUNK 32   // entries per LDS reduction round
 template <bool FX>
@@ -331,7 +336,7 @@ __global__ __launch_bounds__(256) void surfel_composite_bwd_kernel(
     int W, int H, int gx, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const SurfRec* __restrict__ recs,
     const uint4* __restrict__ binfo, const uint32_t* __restrict__ goff, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ med_pos, const float* __restrict__ m1_in,
-    const float* __restrict__ m2_in, const float* __restrict__ m0_in, const float* __restrict__ out_color, const float* __restrict__ out_allmap,
+    const float* __restrict__ m2_in, const float* __restrict__ m0_in, const GsCam* __restrict__ cam,
     const float* __restrict__ dL_dcolor, const float* __restrict__ dL_dallmap, float* __restrict__ rows)
 {
 	__shared__ float pl[SP_BWD_PLANES][256];
@@ -354,7 +359,7 @@ __global__ __launch_bounds__(256) void surfel_composite_bwd_kernel(
 	const uint32_t walk = s_max;   // entries [0, walk) of the list have a contributor somewhere in the tile
 	// upstream gradients (absent = zero) and the forward's totals
 	float gC[3] = {0.f, 0.f, 0.f}, gN[3] = {0.f, 0.f, 0.f}, gD = 0.f, gA = 0.f, gMed = 0.f, gDist = 0.f;
-	float Co[3] = {0.f, 0.f, 0.f}, No[3] = {0.f, 0.f, 0.f}, Do = 0.f, Ao = 0.f, dist2 = 0.f, Af = 0.f, M1f = 0.f, M2f = 0.f, mref = 0.f;
+	float Af = 0.f, M1f = 0.f, M2f = 0.f, mref = 0.f, T = 1.0f;
 	uint32_t medp = 0;
 	if (inside) {
 		if (dL_dcolor != nullptr)
@@ -364,19 +369,17 @@ __global__ __launch_bounds__(256) void surfel_composite_bwd_kernel(
 			for (int c = 0; c < 3; c++) gN[c] = dL_dallmap[(2 + c) * HW + pix];
 			gMed = dL_dallmap[5 * HW + pix]; gDist = dL_dallmap[6 * HW + pix];
 		}
-		for (int c = 0; c < 3; c++) { Co[c] = out_color[c * HW + pix]; No[c] = out_allmap[(2 + c) * HW + pix]; }
-		Do = out_allmap[pix];
-		Ao = out_allmap[HW + pix];
-		dist2 = 2.0f * out_allmap[6 * HW + pix];
-		Af = 1.0f - final_T[slot];
+		T = final_T[slot];   // T behind the pixel's last contributor
+		Af = 1.0f - T;
 		M1f = m1_in[slot];
 		M2f = m2_in[slot];
 		mref = m0_in[slot];
 		medp = med_pos[slot];
 	}
-	float T = 1.0f, aC[3] = {0.f, 0.f, 0.f}, aN[3] = {0.f, 0.f, 0.f}, aD = 0.f, aA = 0.f, aWG = 0.f;
-	uint32_t contributor = 0;
-	for (uint32_t base = range.x; base < range.x + walk; base += 256) {
+	// R_{i+1} of every composited quantity: colour (behind the last contributor: the background), normal, depth, alpha, ddist/dw
+	float rC[3] = {cam->bg[0], cam->bg[1], cam->bg[2]}, rN[3] = {0.f, 0.f, 0.f}, rD = 0.f, rA = 0.f, rWG = 0.f;
+	for (int b = (int)((walk + 255u) / 256u) - 1; b >= 0; b--) {
+		const uint32_t base = range.x + 256u * (uint32_t)b;
 		__syncthreads();   // the previous batch's planes are no longer read
 		const uint32_t j = base + (uint32_t)tid;
 		if (j < range.y) {
@@ -387,16 +390,16 @@ __global__ __launch_bounds__(256) void surfel_composite_bwd_kernel(
 		}
 		__syncthreads();
 		const int cnt = (int)min(256u, range.x + walk - base);
-		for (int c0 = 0; c0 < cnt; c0 += SURF_CHUNK) {
+		for (int c0 = ((cnt - 1) / SURF_CHUNK) * SURF_CHUNK; c0 >= 0; c0 -= SURF_CHUNK) {
 			const int ce = min(SURF_CHUNK, cnt - c0);
-			for (int el = 0; el < ce; el++) {
+			for (int el = ce - 1; el >= 0; el--) {
 				const int e = c0 + el;
+				const uint32_t contributor = 256u * (uint32_t)b + (uint32_t)e + 1u;   // the forward's 1-based list position
 				float gr[GSR_SURF_ROW];
 #pragma unroll
 				for (int k = 0; k < GSR_SURF_ROW; k++) gr[k] = 0.f;
 				bool act = false;
-				if (contributor < last) {
-					contributor++;
+				if (contributor <= last) {
 					const float Tu[3] = {pl[SP_TU][e], pl[SP_TU + 1][e], pl[SP_TU + 2][e]};
 					const float Tv[3] = {pl[SP_TV][e], pl[SP_TV + 1][e], pl[SP_TV + 2][e]};
 					const float Tw[3] = {pl[SP_TW][e], pl[SP_TW + 1][e], pl[SP_TW + 2][e]};
@@ -404,23 +407,27 @@ __global__ __launch_bounds__(256) void surfel_composite_bwd_kernel(
 					SurfHit h;
 					if (surf_eval(Tu, Tv, Tw, pl[SP_CX][e], pl[SP_CY][e], o, px, py, FX, h)) {
 						act = true;
+						const float inv = 1.0f / (1.0f - h.alpha);
+						T = T * inv;   // T_i, before this entry
 						const float w = h.alpha * T;
 						const float m = surf_m(h.z) - mref;   // (the forward's shift: g and ddist/dm are shift-invariant)
 						const float n[3] = {pl[SP_N][e], pl[SP_N + 1][e], pl[SP_N + 2][e]};
 						const float col[3] = {pl[SP_RGB][e], pl[SP_RGB + 1][e], pl[SP_RGB + 2][e]};
 						const float gw = ((m * m) * Af + M2f) - (2.0f * m) * M1f;   // ddist / dw_i
-						for (int c = 0; c < 3; c++) { aC[c] += w * col[c]; aN[c] += w * n[c]; }
-						aD += w * h.z;
-						aA += w;
-						aWG += w * gw;
-						const float inv = 1.0f / (1.0f - h.alpha);
-						float dA = gA * (T - (Ao - aA) * inv) + gD * (T * h.z - (Do - aD) * inv) + gDist * (T * gw - (dist2 - aWG) * inv);
+						const float om = 1.0f - h.alpha;
+						float dA = gA * (1.0f - rA) + gD * (h.z - rD) + gDist * (gw - rWG);
 						for (int c = 0; c < 3; c++) {
-							dA += gC[c] * (T * col[c] - (Co[c] - aC[c]) * inv);
-							dA += gN[c] * (T * n[c] - (No[c] - aN[c]) * inv);
+							dA += gC[c] * (col[c] - rC[c]);
+							dA += gN[c] * (n[c] - rN[c]);
 							gr[10 + c] = w * gC[c];
 							gr[13 + c] = w * gN[c];
+							rC[c] = h.alpha * col[c] + om * rC[c];
+							rN[c] = h.alpha * n[c] + om * rN[c];
 						}
+						dA *= T;
+						rA = h.alpha + om * rA;
+						rD = h.alpha * h.z + om * rD;
+						rWG = h.alpha * gw + om * rWG;
 						// dL/dz: expected depth, median (the forward's recorded contributor), distortion through m
 						float dz = gD * w + gDist * (2.0f * w * (m * Af - M1f)) *
 						                        ((GSR_SURF_FAR / (GSR_SURF_FAR - GSR_SURF_NEAR)) * GSR_SURF_NEAR / (h.z * h.z));
@@ -448,7 +455,6 @@ __global__ __launch_bounds__(256) void surfel_composite_bwd_kernel(
 						} else {
 							gr[8] += dz;   // low-pass branch: z = Tw.z, the centre is not differentiated
 						}
-						T = T * (1.0f - h.alpha);
 					}
 				}
 				if (__ballot(act) != 0ull) {
@@ -482,15 +488,15 @@ __global__ __launch_bounds__(256) void surfel_composite_bwd_kernel(
 void launch_surfel_composite_bwd(const ImgLayout& il, int W, int H, const uint2* ranges, const uint32_t* point_list, const SurfRec* recs,
                                  const uint4* binfo, const uint32_t* goff, const float* final_T,
                                  const uint32_t* n_contrib, const uint32_t* med_pos, const float* m1, const float* m2, const float* m0,
-                                 const float* out_color, const float* out_allmap, const float* dL_dcolor, const float* dL_dallmap,
+                                 const GsCam* cam, const float* dL_dcolor, const float* dL_dallmap,
                                  float* rows, bool fast_exp, hipStream_t s)
 {
 	if (fast_exp)
 		hipLaunchKernelGGL(surfel_composite_bwd_kernel<true>, dim3(il.T), dim3(256), 0, s, W, H, il.gx, ranges, point_list, recs, binfo,
-		                   goff, final_T, n_contrib, med_pos, m1, m2, m0, out_color, out_allmap, dL_dcolor, dL_dallmap, rows);
+		                   goff, final_T, n_contrib, med_pos, m1, m2, m0, cam, dL_dcolor, dL_dallmap, rows);
 	else
 		hipLaunchKernelGGL(surfel_composite_bwd_kernel<false>, dim3(il.T), dim3(256), 0, s, W, H, il.gx, ranges, point_list, recs, binfo,
-		                   goff, final_T, n_contrib, med_pos, m1, m2, m0, out_color, out_allmap, dL_dcolor, dL_dallmap, rows);
+		                   goff, final_T, n_contrib, med_pos, m1, m2, m0, cam, dL_dcolor, dL_dallmap, rows);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 contract gsr_surfel.hip implements (INTEGRATION.md "2D Gaussian surfels").  Per pixel over the same square-rect tile lists and
 the same (depth, index) order; gradients come from autograd, the documented stop-gradients are `.detach()`.
 
-    out = render(...)            # dict: color [3,H,W], allmap [7,H,W], radii [P], M [P,3,3], events [H,W]
+    out = render(...)            # dict: color [3,H,W], allmap [7,H,W], radii [P], M [P,3,3], events [H,W],
+                                 #       n_contrib [H,W] (the kernel's `last`), stopped [H,W], rects [P,4] (tiles: x0 y0 x1 y1)
     grads(out, leaves, ...)      # autograd gradients, plus means2D from dL/dM (the 2DGS densification proxy)
 
 Runs on any device; the GPU tests run it on the GPU in float64."""
@@ -12,7 +13,7 @@ import numpy as np
 import torch
 
 # the compatibility contract (gsr_common.h GSR_SURF_*)
-NEAR = 0.2
+NEAR = float(np.float32(0.2))     # 0.2f, the kernel's constant: a surfel at exactly this view depth is culled on both sides
 FAR = 100.0
 LOWPASS = 2.0
 CUTOFF = 3.0
@@ -130,10 +131,16 @@ def own_radii(means3D, scales, rotations, viewmatrix, projmatrix, W, H, scale_mo
 
 
 def render(means3D, opacities, scales, rotations, viewmatrix, projmatrix, campos, W, H, bg, scale_modifier=1.0, sh_degree=0,
-           shs=None, colors_precomp=None, radii=None):
+           shs=None, colors_precomp=None, radii=None, dtype=torch.float64, near_skip=True):
     """Float64 forward.  Tensors may require grad.  `radii` (int, [P]): use these radii (visibility and rect size) instead of
-    the model's own -- the GPU tests pass the operator's radii so that the tile lists agree."""
-    dt = torch.float64
+    the model's own -- the GPU tests pass the operator's radii so that the tile lists agree.  `dtype`: the arithmetic of the
+    whole model (the inputs are expected in it); torch.float32 gives a second, independently ordered float32 evaluation of the
+    operator, against which the float64 one measures what float32 can hold.  The sort key is _view_z_f32 in either.
+
+    Besides the images: `n_contrib` [H,W] int64, the 1-based list position of the pixel's last contributor (0: none), and
+    `stopped` [H,W] bool, true where the walk ended on the T (1 - alpha) < T_MIN rule rather than at the list's end.
+    `near_skip=False` drops the per-pixel skip z < NEAR (not the cull): a scene on which that changes nothing does not test it."""
+    dt = dtype
     dev = means3D.device
     view = viewmatrix.to(dt)
     proj = projmatrix.to(dt)
@@ -185,6 +192,8 @@ def render(means3D, opacities, scales, rotations, viewmatrix, projmatrix, campos
     allmap = torch.zeros(7, H, W, dtype=dt, device=dev)
     color = color + bg.to(dt).reshape(3, 1, 1)
     events = torch.zeros(H, W, dtype=torch.bool, device=dev)
+    n_contrib = torch.zeros(H, W, dtype=torch.int64, device=dev)
+    stopped = torch.zeros(H, W, dtype=torch.bool, device=dev)
     ids = np.array(sorted(rects), dtype=np.int64)
     key = _view_z_f32(means3D.detach().float().cpu().numpy(), viewmatrix.float().cpu().numpy().reshape(-1))
     order = ids[np.lexsort((ids, key[ids]))] if len(ids) else ids
@@ -198,17 +207,23 @@ def render(means3D, opacities, scales, rotations, viewmatrix, projmatrix, campos
             if not lst:
                 continue
             L = torch.tensor(lst, device=dev)
-            c_out, a_out, ev = _composite(xs.to(dt), ys.to(dt), Tu[L], Tv[L], Tw[L], cx[L].detach(), cy[L].detach(), op[L], n[L], rgb[L],
-                                          bg.to(dt), M[L].detach())
+            c_out, a_out, ev, nc, st = _composite(xs.to(dt), ys.to(dt), Tu[L], Tv[L], Tw[L], cx[L].detach(), cy[L].detach(), op[L], n[L], rgb[L],
+                                          bg.to(dt), M[L].detach(), near_skip)
             imgs_c.append(c_out)
             imgs_a.append(a_out)
             idx_pix.append(ys * W + xs)
             events[ys, xs] = ev
+            n_contrib[ys, xs] = nc
+            stopped[ys, xs] = st
     if idx_pix:
         pix = torch.cat(idx_pix)
         color = color.reshape(3, H * W).index_copy(1, pix, torch.cat(imgs_c, 1)).reshape(3, H, W)
         allmap = allmap.reshape(7, H * W).index_copy(1, pix, torch.cat(imgs_a, 1)).reshape(7, H, W)
-    return dict(color=color, allmap=allmap, radii=torch.tensor(out_radii), M=M, events=events)
+    rect_t = torch.zeros(P, 4, dtype=torch.int64)
+    for i, r in rects.items():
+        rect_t[i] = torch.tensor(r)
+    return dict(color=color, allmap=allmap, radii=torch.tensor(out_radii), M=M, events=events, n_contrib=n_contrib, stopped=stopped,
+                rects=rect_t)
 
 
 def _excl_cumprod(x):
@@ -242,9 +257,10 @@ def _eval_f32(px, py, M, o):
     return alpha.double(), z.double()
 
 
-def _composite(px, py, Tu, Tv, Tw, cx, cy, o, n, rgb, bg, M):
-    """One tile: pixels [n] x list entries [L] (front to back).  Returns colour [3,n], allmap [7,n] and the per-pixel flag of a
-    threshold event: a decision within 1e-3 relative of its threshold.  The four of the contract -- alpha vs 1/255, T vs 1e-4,
+def _composite(px, py, Tu, Tv, Tw, cx, cy, o, n, rgb, bg, M, near_skip=True):
+    """One tile: pixels [n] x list entries [L] (front to back).  Returns colour [3,n], allmap [7,n], the per-pixel flag of a
+    threshold event, the 1-based position of the pixel's last contributor (0: none) and whether the T_MIN rule ended its walk.
+    A threshold event is a decision within 1e-3 relative of its threshold.  The four of the contract -- alpha vs 1/255, T vs 1e-4,
     rho3 vs rho2, z vs NEAR -- and, a DELIBERATE WIDENING beyond them, three more: o G vs the 0.99 clamp, T vs 0.5 at the median,
     and an ill-conditioned contributor (_eval_f32: its float32 alpha or depth is off by more than 2e-5 -- a splat seen almost
     edge-on; measured: 3 of the 4 pixels beyond 1e-4 in the GPU tests' two largest scenes were of this kind, the fourth a
@@ -261,7 +277,8 @@ def _composite(px, py, Tu, Tv, Tw, cx, cy, o, n, rgb, bg, M):
     in3 = (rho3 <= rho2).detach()
     rho = torch.where(in3, rho3, rho2)
     z = torch.where(in3, u * Tw[None, :, 0] + v * Tw[None, :, 1] + Tw[None, :, 2], Tw[None, :, 2].expand_as(u))
-    ok = ok & (z.detach() >= NEAR)
+    if near_skip:
+        ok = ok & (z.detach() >= NEAR)
     G = torch.exp(-0.5 * rho)
     alpha = torch.clamp(o[None] * G, max=ALPHA_MAX)         # clamped: no gradient
     ok = ok & (alpha.detach() >= ALPHA_MIN)
@@ -292,13 +309,14 @@ def _composite(px, py, Tu, Tv, Tw, cx, cy, o, n, rgb, bg, M):
     ev = (((ad - ALPHA_MIN).abs() < rel * ALPHA_MIN) & (ad > 0)) | ((o[None].detach() * G.detach() - ALPHA_MAX).abs() < rel)
     ev = ev | (((Tbd * (1 - ad) - T_MIN).abs() < rel * T_MIN) & ok & (torch.cumsum(stop.int(), 1) <= 1))
     ev = ev | (((rho3 - rho2).detach().abs() < rel * (rho2.detach() + 1e-6)) & (ad > ALPHA_MIN * 0.5))
-    ev = ev | (((z.detach() - NEAR).abs() < rel) & (ad > 0))
+    ev = ev | (((z.detach() - NEAR).abs() < rel) & (ad > ALPHA_MIN * 0.5))      # (an entry far below 1/255 contributes either way)
     ev = ev | (((Tbd - MEDIAN_T).abs() < rel) & con)
     a32, z32 = _eval_f32(px, py, M, o)
     ev = ev | (con & (((a32 - ad).abs() > 2e-5) | ((z32 - z.detach()).abs() > 2e-5)))
     ev = ev.any(1)
     allmap = torch.stack([D, 1 - Tf, Nn[:, 0], Nn[:, 1], Nn[:, 2], median, dist], 0)
-    return C.T, allmap, ev
+    n_contrib = torch.where(con, idx + 1, torch.zeros_like(idx)).max(1).values
+    return C.T, allmap, ev, n_contrib, stop.any(1)
 
 
 def grads(out, leaves, g_color=None, g_allmap=None, W=None, H=None):

@@ -139,3 +139,43 @@ def test_cov3D_precomp_is_refused():
     m, o = torch.zeros(2, 3), torch.zeros(2, 1)
     with pytest.raises(ValueError, match=r"cov3D_precomp is not supported.*\(2, 6\).*3D-Gaussian covariance"):
         r(m, m, o, colors_precomp=torch.zeros(2, 3), cov3D_precomp=torch.zeros(2, 6))
+
+
+# ---- n_contrib, stopped and the float32 mode (used by the scene preconditions and the per-surfel tolerance) ----
+def test_two_splats_n_contrib_and_stopped():
+    out = _render([[0.0, 0.0, 4.0], [0.0, 0.0, 7.0]], [0.5, 0.7], [[0.3, 0.3], [0.3, 0.3]], [[1.0, 0, 0, 0], [1.0, 0, 0, 0]],
+                  [[1.0, 0, 0], [0, 1.0, 0]])
+    nc, st = out["n_contrib"], out["stopped"]
+    assert nc.dtype == torch.int64 and st.dtype == torch.bool and nc.shape == (H, W) == st.shape
+    assert int(nc[CY, CX]) == 2 and not bool(st.any())           # both contribute at the centre; T never nears 1e-4
+    assert int(nc[0, 0]) == 0                                     # a corner far outside both footprints (the tile lists hold them)
+    assert set(nc.unique().tolist()) <= {0, 1, 2}
+    assert bool(((nc > 0) == (out["allmap"][1] > 0)).all())
+    assert out["rects"].shape == (2, 4) and bool((out["rects"][:, 2] > out["rects"][:, 0]).all())
+
+
+def test_stop_rule_sets_stopped_and_ends_n_contrib():
+    # four splats of alpha 0.99 at the centre: T = 1e-2, 1e-4, then T (1 - alpha) = 1e-6 < 1e-4 at the third: the walk stops there,
+    # the third and fourth do not contribute
+    z = [3.0, 4.0, 5.0, 6.0]
+    out = _render([[0.0, 0.0, v] for v in z], [1.0] * 4, [[0.3, 0.3]] * 4, [[1.0, 0, 0, 0]] * 4, [[1.0, 0, 0]] * 4)
+    assert int(out["n_contrib"][CY, CX]) == 2 and bool(out["stopped"][CY, CX])
+    assert out["allmap"][1, CY, CX].item() == pytest.approx(1 - 0.01 * 0.01, rel=1e-12)
+    assert not bool(out["stopped"][0, 0])
+
+
+@pytest.mark.parametrize("o1,expect_first", [(0.3, False), (0.6, True)])
+def test_median_rule_n_contrib_and_float32_mode(o1, expect_first):
+    args = ([[0.0, 0.0, 4.0], [0.0, 0.0, 7.0]], [o1, 0.5], [[0.3, 0.3], [0.3, 0.3]], [[1.0, 0, 0, 0], [1.0, 0, 0, 0]], [[1.0, 0, 0], [0, 1.0, 0]])
+    out = _render(*args)
+    assert int(out["n_contrib"][CY, CX]) == 2 and not bool(out["stopped"].any())    # the median moves, the last contributor does not
+    cam = _cam()
+    f = torch.float32
+    t = [torch.tensor(a, dtype=f) for a in args]
+    o32 = sm.render(t[0], t[1].reshape(-1, 1), t[2], t[3], cam.viewmatrix, cam.projmatrix, cam.campos, W, H, torch.zeros(3, dtype=f),
+                    colors_precomp=t[4], dtype=f)
+    assert o32["color"].dtype == f and o32["allmap"].dtype == f and o32["M"].dtype == f
+    assert torch.equal(o32["n_contrib"], out["n_contrib"]) and torch.equal(o32["radii"], out["radii"])
+    assert o32["allmap"][5, CY, CX].item() == pytest.approx(4.0 if expect_first else 7.0, rel=1e-6)
+    d = (o32["allmap"].double() - out["allmap"]).abs().max().item()
+    assert 0 < d < 1e-5                                           # float32 arithmetic: close, and not the float64 result recast

@@ -3,7 +3,7 @@
 
 The tables are DERIVED here, not transcribed: for every sign configuration of the eight cube corners the
 isosurface inside the cube is assembled from oriented segments on the six faces and the resulting closed loops are
-fan-triangulated.  Corner / edge numbering is the usual one (Lorensen & Cline 1987 as popularised by P. Bourke):
+fan-triangulated from an apex chosen so that no fan diagonal lies in a cube face (see case_triangles).  Corner / edge numbering is the usual one (Lorensen & Cline 1987 as popularised by P. Bourke):
 
     corners  0:(0,0,0) 1:(1,0,0) 2:(1,1,0) 3:(0,1,0) 4:(0,0,1) 5:(1,0,1) 6:(1,1,1) 7:(0,1,1)
     edges    0:0-1 1:1-2 2:2-3 3:3-0 4:4-5 5:5-6 6:6-7 7:7-4 8:0-4 9:1-5 10:2-6 11:3-7
@@ -13,7 +13,10 @@ outside the cube; on a face a segment runs from the crossing where the boundary 
 the crossing where it leaves it, which makes every loop wind counter-clockwise seen from the outside (tsdf > 0) side:
 triangle normals point from inside to outside (checked numerically for all 256 cases, tests/test_tsdf.py).  On an ambiguous face (inside corners on a diagonal) the two inside
 corners are cut off separately; the rule only looks at the face's four signs, so both cubes sharing the face agree and
-the mesh is watertight.  tests/test_tsdf.py checks orientation for all 256 cases and closedness on sampled fields.
+the mesh is watertight.  A triangle edge that is not one of these face segments is a diagonal of a loop; it never joins two
+cube edges of one cube face, so it runs through the cube's interior and belongs to this cube alone: every edge of the mesh
+is used once per direction, on ambiguous faces too.  tests/test_tsdf.py checks orientation and the diagonals for all 256
+cases, and closedness on smooth and on random sign fields.
 """
 import os
 
@@ -50,7 +53,18 @@ def face_segments(case, face):
     return segs
 
 
+def share_face(e0, e1):
+    """True when cube edges e0 and e1 lie on a common cube face."""
+    cs = [CORNERS[c] for c in EDGES[e0] + EDGES[e1]]
+    return any(len({c[d] for c in cs}) == 1 for d in range(3))
+
+
 def case_triangles(case):
+    """Triangles of one case as triples of cube edges.  Every loop is a fan from one of its vertices.  A fan diagonal that
+    joined two cube edges of one cube face would lie IN that face; on an ambiguous face the neighbouring cube's loop can
+    carry the same diagonal, and the two cubes would then emit coplanar triangles that share it in the same direction (a
+    directed edge used twice, four triangles on one edge).  The apex is therefore the first loop vertex whose diagonals
+    all join cube edges without a common face; every loop of the 256 cases has one."""
     if case in (0, 255):
         return []
     nxt = {}
@@ -71,7 +85,10 @@ def case_triangles(case):
             seen.add(e)
             e = nxt[e]
         assert 3 <= len(loop) <= 12, (case, loop)
-        for k in range(1, len(loop) - 1):
+        n = len(loop)
+        apex = next(s for s in range(n) if not any(share_face(loop[s], loop[(s + k) % n]) for k in range(2, n - 1)))
+        loop = loop[apex:] + loop[:apex]              # a rotation: the orientation stays
+        for k in range(1, n - 1):
             tris.append((loop[0], loop[k], loop[k + 1]))
     return tris
 

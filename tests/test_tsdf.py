@@ -13,7 +13,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaustudio_amd", "csrc"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gen_mc_tables as g  # noqa: E402
+import sap_model as sm  # noqa: E402
+import volume_state as vs  # noqa: E402
 
 from oracle import tsdf_pyoracle as to  # noqa: E402
 
@@ -93,6 +96,38 @@ def test_mc_tables_give_closed_consistently_oriented_surfaces():
                 for q in range(3):
                     E[(vid[q], vid[(q + 1) % 3])] += 1
         assert E and all(c == 1 and E.get((b, a), 0) == 1 for (a, b), c in E.items())
+
+
+def test_mc_tables_diagonals_never_lie_in_a_cube_face():
+    """Per case: a triangle edge is either one of the face segments the loops are made of, or a fan diagonal.  A diagonal
+    that joined two cube edges of one cube face would lie in that face, where the neighbouring cube may emit it as well
+    (ambiguous faces): no diagonal does."""
+    table, _ = g.build()
+    for case in range(1, 255):
+        segs = {s for f in g.FACES for s in g.face_segments(case, f)}
+        for t in table[case]:
+            for a, b in ((t[0], t[1]), (t[1], t[2]), (t[2], t[0])):
+                if (a, b) in segs or (b, a) in segs:
+                    continue
+                ca, cb = [g.CORNERS[c] for c in g.EDGES[a]], [g.CORNERS[c] for c in g.EDGES[b]]
+                assert not any(len({c[d] for c in ca + cb}) == 1 for d in range(3)), (case, t, a, b)
+
+
+@pytest.mark.parametrize("shape,seed", [((14, 14, 14), 0), ((14, 14, 14), 1), ((14, 14, 14), 2), ((3, 3, 40), 3)])
+def test_mc_tables_are_manifold_on_random_sign_fields(shape, seed):
+    """Random signs reach what a smooth field never does: every ambiguous face, next to every other case.  Every directed
+    edge occurs exactly once, and every edge that does not lie on the field's boundary has its reverse exactly once.  The
+    second condition (and the first) fails with the table that fanned every loop from its first vertex: 20 of the 358 loops
+    then had a diagonal inside a cube face, which both cubes of an ambiguous face emitted in the same direction."""
+    inside = np.random.default_rng(seed).random(shape) < 0.5
+    _, faces = sm.marching_cubes(np.where(inside, -1.0, 1.0).astype(np.float32), 0.0)
+    case, node, axis = vs.dense_layout(inside)
+    assert len(node) == int(faces.max()) + 1
+    if shape[0] > 3:
+        assert len(vs.cases_present(case)) == 254
+    doubled, missing, interior = vs.edge_topology(faces, node, axis, vs.dense_extractable(shape))
+    assert interior > 0.5 * 3 * len(faces)
+    assert doubled == 0 and missing == 0, (doubled, missing, interior)
 
 
 def test_oracle_wall_scan_zero_crossing_and_running_average():

@@ -9,5 +9,6 @@ from .rasterizer import (  # noqa: F401
 from .options import options  # noqa: F401,E402  (per-call options: tile band, fast_exp, kernel A/B switches)
 from .tsdf_rgbd import ColorTSDFVolume, fuse_rgbd  # noqa: F401,E402  (coloured TSDF fusion of posed RGB-D frames)
 from .visual_hull import VisualHull, carve, visual_hull_init  # noqa: F401,E402  (silhouette carving and Gaussian seeds)
+from .voxelize import VoxelGrid, closest_on_mesh, voxel_init, voxel_seeds, voxelize_mesh  # noqa: F401,E402  (mesh -> voxels -> Gaussian seeds)
 
 __version__ = "0.1.0"

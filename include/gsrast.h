@@ -731,6 +731,54 @@ int gsr_hull_carve(const float* axis_x, const float* axis_y, const float* axis_z
                    const gsr_hull_camera* cameras_host, gsr_hull_camera* cameras_device, int num_cameras, const uint32_t* mask_words,
                    uint64_t num_words, uint8_t* filled, uint32_t* count, int* carved_by, void* stream);
 
+/* ---- mesh voxelization (csrc/gsr_voxel.hip): the `VoxelInitializer`'s hot path, gaustudio/pipelines/initializers/mesh.py:252-442 ----
+ * A triangle mesh (vertices[num_vertices,3] f64, faces[num_faces,3] i32, device memory) against the grid [n0,n1,n2] of cubic
+ * voxels of edge voxel_size whose lower corner is min_bound[3] (HOST): 2 <= n_d <= GSR_VOXEL_MAX_RES, voxel_size > 0.  All
+ * arithmetic is float64, operation for operation that of tests/mesh_voxel_model.py: Akenine-Moller's triangle / box test with
+ * its exact comparisons (touching overlaps) around the box centre (min_bound + voxel_size / 2) + i voxel_size.  Arrays are
+ * caller-owned device memory, scratch comes from the gsr_alloc_fn callback (once per call), `stream` is the HIP stream of every
+ * launch, a count that sizes the next stage's arrays is written to HOST memory after one wait on `stream`.  The stages:
+ *
+ * gsr_voxel_plan:  validates the mesh -- GSR_ERR_ARG for a face index outside [0, num_vertices), a vertex coordinate that is
+ *   not finite, a bad grid, or more than GSR_VOXEL_MAX_ITEMS work items, with nothing written to the caller's arrays -- and
+ *   writes per triangle tri_box[num_faces,6] = (lo0, lo1, lo2, hi0, hi1, hi2), its inclusive index-space box widened by one
+ *   voxel and clamped to the grid, and col_start[num_faces + 1], the exclusive scan of its number of (i0, i1) columns.
+ *   *num_items = the number of (triangle, column) work items.
+ * gsr_voxel_count: item_start[num_items + 1] = exclusive scan of the overlaps of each work item; *num_pairs = their number
+ *   (GSR_ERR_ARG beyond GSR_VOXEL_MAX_ITEMS).  A work item tests only the i2 range its triangle's plane can reach in the
+ *   column, one voxel wider either side (the whole box range when the normal's component along i2 is too small to bound the
+ *   error): a filter, the overlap test alone decides.
+ * gsr_voxel_emit:  pair_voxel[num_pairs] (linear index (i0 n1 + i1) n2 + i2) and pair_tri[num_pairs] in work-item order
+ *   (triangles ascending).  No wait.
+ * gsr_voxel_sort:  stable radix sort of the pairs by voxel (only the digits n0 n1 n2 needs), head flags, scan:
+ *   voxel_index[num_voxels] ascending, pair_start[num_voxels + 1], pair_tri[num_pairs] (triangles ascending within a voxel),
+ *   and, when not NULL, grid_index[num_voxels,3] and occupancy[ceil(n0 n1 n2 / 32)] (bit t & 31 of word t >> 5; zeroed by the
+ *   call).  Size voxel_index / pair_start / grid_index for num_pairs voxels; *num_voxels says how many there are.
+ * gsr_voxel_closest: per occupied voxel, Ericson's closest point on a triangle from the voxel centre ((i + 0.5) voxel_size) +
+ *   min_bound over the triangles listed in the 27 voxels around it: closest_tri[num_voxels] (smallest d2, exact ties to the
+ *   lower triangle, a d2 that is not finite never wins; -1 = none), closest_uvw[num_voxels,3] f64 = (1 - v - w, v, w) (0 for
+ *   -1) and, when color is not NULL, color[num_voxels,3] f32 = c0 u + c1 v + c2 w in f64 of vertex_colors[num_vertices,3] f32,
+ *   rounded once (0.5 for -1).  A listed triangle or face index out of range is skipped.  No wait.
+ * Bit-identical from run to run (no float atomics). */
+#define GSR_VOXEL_MAX_RES 1024
+#define GSR_VOXEL_MAX_ITEMS (1 << 30)
+int gsr_voxel_plan(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const double* vertices, int num_vertices, const int* faces,
+                   int num_faces, double voxel_size, const double* min_bound, int n0, int n1, int n2, int* tri_box, int* col_start,
+                   int* num_items, void* stream);
+int gsr_voxel_count(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const double* vertices, const int* faces, int num_faces,
+                    double voxel_size, const double* min_bound, int n0, int n1, int n2, const int* tri_box, const int* col_start,
+                    int num_items, int* item_start, int* num_pairs, void* stream);
+int gsr_voxel_emit(const double* vertices, const int* faces, int num_faces, double voxel_size, const double* min_bound, int n0, int n1,
+                   int n2, const int* tri_box, const int* col_start, int num_items, const int* item_start, uint32_t* pair_voxel,
+                   int* pair_tri, void* stream);
+int gsr_voxel_sort(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const uint32_t* pair_voxel, const int* pair_tri_in, int num_pairs,
+                   int n0, int n1, int n2, uint32_t* voxel_index, int* pair_start, int* pair_tri, int* grid_index, uint32_t* occupancy,
+                   int* num_voxels, void* stream);
+int gsr_voxel_closest(const double* vertices, int num_vertices, const int* faces, int num_faces, const float* vertex_colors,
+                      double voxel_size, const double* min_bound, int n0, int n1, int n2, const uint32_t* voxel_index,
+                      const int* pair_start, const int* pair_tri, int num_voxels, int* closest_tri, double* closest_uvw, float* color,
+                      void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

@@ -779,6 +779,49 @@ int gsr_voxel_closest(const double* vertices, int num_vertices, const int* faces
                       const int* pair_start, const int* pair_tri, int num_voxels, int* closest_tri, double* closest_uvw, float* color,
                       void* stream);
 
+/* ---- vertex-colour baking and per-triangle Gaussian seeds: the per-view body of gaustudio/scripts/texture_mesh.py:108-141
+ * and MeshInitializer.build_model (gaustudio/pipelines/initializers/mesh.py:20-250) for a mesh that stays in HBM.  Additive
+ * to ABI 6, in the style of gsr_mesh_*: inputs and outputs are caller-owned device memory, `stream` is the HIP stream of
+ * every launch, intrinsics (3x3 row-major K; fx, fy, cx, cy are read) and extrinsics (4x4 row-major world-to-camera, OpenCV
+ * axes) are HOST pointers.  float32 throughout, correctly rounded divide / sqrt; no FMA in the two bake entries, the explicit
+ * ones named below in gsr_mesh_seeds; deterministic (no atomics on any result).  Contract: INTEGRATION.md s21; design: gsr_mesh_bake.hip, DESIGN.md s18. ---- */
+
+/* One view's facing filter.  For every face with visible[f] != 0 (u8, gsr_mesh_visible_faces): n = (v1 - v0) x (v2 - v0),
+ * cos = (n / |n|) . d with d the normalised third row of the world-to-camera rotation; cos < -0.05f selects the face and
+ * writes stamp[v] = seq (seq >= 0) for its three vertices, by plain stores.  stamp[num_verts] i32 is the caller's, set to -1
+ * once per bake, never cleared between views.  cos_out[num_faces] f32 (may be NULL) receives cos, NaN for a face that is not
+ * visible.  A degenerate face (|n| = 0: cos = NaN) and a face with an index outside [0, num_verts) select nothing.  No wait.
+ * GSR_ERR_ARG for a non-finite matrix or a viewing axis without length. */
+int gsr_mesh_bake_select(const float* verts, int num_verts, const int* faces, int num_faces, const unsigned char* visible,
+                         const float extrinsics[16], int seq, int* stamp, float* cos_out, void* stream);
+
+/* One view's colour lookup, for every vertex with stamp[v] == seq.  image[height,width,3] f32 (device).  exact == 0, the
+ * reference: x = (fx (-x_c)) / z_c + cx, y likewise (PyTorch3D's screen camera after the script's RDF->LUF flip: 2 cx - u),
+ * g_x = 2 (x / (width - 1)) - 1, g_y = 2 (y / (height - 1)) - 1, valid when both lie in [-1, 1]; then grid_sample(bilinear,
+ * align_corners=False, padding reflection) of the image flipped in both axes: i_x = ((g_x + 1) width - 1) / 2 clipped to
+ * [0, width - 1], four taps summed in nw, ne, sw, se order, a tap at column `width` or row `height` skipped.  exact != 0:
+ * u = (fx x_c) / z_c + cx, v likewise, valid when 0 <= u <= width and 0 <= v <= height, the unflipped image sampled at column
+ * u - 0.5, row v - 0.5 by the same rule.  A valid vertex writes colors[v] (3 f32, clamped to [0, 1]) and baked_by[v] = seq;
+ * every other entry of colors[num_verts,3] / baked_by[num_verts] stays as it is.  z_c is not tested (a vertex behind the
+ * camera can be valid, as in the reference).  No wait.  GSR_ERR_ARG for a bad size (> 16384) or singular intrinsics. */
+int gsr_mesh_bake_sample(const float* verts, int num_verts, const int* stamp, int seq, const float intrinsics[9],
+                         const float extrinsics[16], const float* image, int height, int width, int exact, float* colors,
+                         int* baked_by, void* stream);
+
+/* MeshInitializer.build_model: n_per_triangle (1, 3, 4 or 6) flat Gaussians per face, Gaussian g = f * n + k.  With the
+ * barycentric table b_k of mesh.py:98-137: xyz = (b0 v0 + b1 v1) + b2 v2; f_dc = (rgb - 0.5) / C0 with rgb the same sum of
+ * vertex_colors, or 1 when vertex_colors is NULL; scale = (l, l, log(1e-7)) with l = log(2 s + 1e-7), s = max(min edge
+ * length * radius_n, 0), each logarithm float(log(double(x))); rot = rotmat2quaternion(normal2rotation(N)) (w, x, y, z; not
+ * normalised) of N = the same sum of normals[num_verts,3], normalised twice with x / max(|x|, 1e-12), torch.cross taken along
+ * the last axis.  In this entry every norm is |x| = sqrt(fma(x.z, x.z, fma(x.y, x.y, x.x * x.x))) (the edge lengths and the three
+ * normalisations) and the cross product is a x b = (fma(a.y, b.z, -(a.z * b.y)), fma(a.z, b.x, -(a.x * b.z)),
+ * fma(a.x, b.y, -(a.y * b.x))), the forms torch's CPU kernels evaluate; every other operation is a single float32 operation
+ * in the order written in INTEGRATION.md s21.  Outputs xyz / f_dc / scale [num_faces * n, 3] and rot [num_faces * n, 4] f32.  Waits on `stream` once;
+ * GSR_ERR_ARG for another n_per_triangle, num_faces * n >= 2^31 or a face index outside [0, num_verts). */
+int gsr_mesh_seeds(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* verts, const float* normals,
+                   const float* vertex_colors, int num_verts, const int* faces, int num_faces, int n_per_triangle, float* xyz,
+                   float* f_dc, float* scale, float* rot, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

@@ -225,12 +225,16 @@ __device__ __forceinline__ void scan_cells(WaveTopK& t, int k, int lane, int cs,
 __global__ void __launch_bounds__(256) knn_query(Grid g, const unsigned long long* __restrict__ keys, const int* __restrict__ start,
                                                  const int* __restrict__ cnt, const int* __restrict__ cells, int ncells,
                                                  const float4* __restrict__ spts, const float* __restrict__ queries, int nq, int k,
-                                                 double* __restrict__ dist2, int64_t* __restrict__ idx)
+                                                 double* __restrict__ dist2, int64_t* __restrict__ idx, int* __restrict__ qbad)
 {
 	const int lane = threadIdx.x & 63;
 	const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (q >= nq) return;   // wave-uniform
 	const float qx = queries[3 * (size_t)q], qy = queries[3 * (size_t)q + 1], qz = queries[3 * (size_t)q + 2];
+	if (!(isfinite(qx) && isfinite(qy) && isfinite(qz))) {   // wave-uniform: no distance to order by; the host reports it
+		if (lane == 0) atomicOr(qbad, 1);
+		return;
+	}
 	const int cx = qcell_of(qx, g.ox, g.inv_h), cy = qcell_of(qy, g.oy, g.inv_h), cz = qcell_of(qz, g.oz, g.inv_h);
 	WaveTopK t{HUGE_VAL, NO_INDEX, HUGE_VAL, NO_INDEX};
 	bool done = false;
@@ -336,7 +340,7 @@ int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, in
 	int bbox[7];
 	KN_TRY(hipMemcpyAsync(bbox, counters + 8, sizeof(bbox), hipMemcpyDeviceToHost, s));
 	KN_TRY(hipStreamSynchronize(s));
-	if (bbox[6]) return GSR_ERR_ARG;   // a non-finite coordinate
+	if (bbox[6]) return GSR_ERR_NONFINITE;
 	double lo[3], ext = 0.0;
 	for (int a = 0; a < 3; a++) {
 		lo[a] = unordered(bbox[a]);
@@ -367,10 +371,16 @@ int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, in
 	int ncells = 0;
 	KN_TRY(hipMemcpyAsync(&ncells, counters + 2, sizeof(int), hipMemcpyDeviceToHost, s));
 	KN_TRY(hipStreamSynchronize(s));
-	if (nq > 0)
+	if (nq > 0)   // counters[3] (zeroed with the grid's counters): set by a query that is not finite
 		hipLaunchKernelGGL(knn_query, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, g, keys, start, cnt, cells, ncells, spts,
-		                   queries, nq, k, dist2, idx);
+		                   queries, nq, k, dist2, idx, counters + 3);
 	KN_TRY(hipGetLastError());
+	if (nq > 0 && queries != pts) {   // the points themselves were checked with the bounding box
+		int qbad = 0;
+		KN_TRY(hipMemcpyAsync(&qbad, counters + 3, sizeof(int), hipMemcpyDeviceToHost, s));
+		KN_TRY(hipStreamSynchronize(s));
+		if (qbad) return GSR_ERR_NONFINITE_QUERY;
+	}
 	return GSR_OK;
 }
 

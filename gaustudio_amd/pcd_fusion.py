@@ -68,7 +68,14 @@ def _points(name, p):
     return _device_tensor(name, p, 3, (torch.float32, torch.float64))
 
 
+_ERR_NONFINITE, _ERR_NONFINITE_QUERY = -5, -6   # GSR_ERR_NONFINITE, GSR_ERR_NONFINITE_QUERY (include/gsrast.h)
+
+
 def _rc(name, rc):
+    if rc == _ERR_NONFINITE:
+        raise ValueError(f"{name}: a point coordinate is not finite")
+    if rc == _ERR_NONFINITE_QUERY:
+        raise ValueError(f"{name}: a coordinate of the queries is not finite")
     if rc < 0:
         raise RuntimeError(f"{name} failed (rc={rc})")
     return rc
@@ -78,7 +85,9 @@ def _rc(name, rc):
 def knn(points, k, queries=None):
     """Exact k nearest neighbours of each query (default: each point) among `points` [N,3] (float32, or float64 holding
     float32 values): (dist2 [Q,k] float64, idx [Q,k] int64) in ascending (squared distance, index) order, the distances in
-    float64 from the float32 coordinates (what cKDTree computes on the same values).  1 <= k <= 64, k <= N."""
+    float64 from the float32 coordinates (what cKDTree computes on the same values).  1 <= k <= 64, k <= N.  Ties are
+    broken by the index, so the output is fully determined.  Empty queries ([0,3]) give empty [0,k] outputs; a NaN or
+    infinite coordinate, of the points or of the queries, raises ValueError."""
     pts = _points("points", points)
     q = None if queries is None else _points("queries", queries)
     _check_k(k, pts.shape[0])
@@ -92,12 +101,13 @@ def knn(points, k, queries=None):
     dist2 = torch.empty((nq, k), dtype=torch.float64, device=pts.device)
     idx = torch.empty((nq, k), dtype=torch.int64, device=pts.device)
     ws = _Workspace(pts.device)
+    # an empty `queries` has no address to pass (a NULL pointer means "the points themselves"): the points' address
+    # stands in for it, and with num_queries = 0 nothing is read through it
+    qptr = _C._ptr(pts) if q is not None and nq == 0 else _C._ptr(q)
     with torch.cuda.device(pts.device):
-        rc = _C.lib().gsr_knn(ws.fn, None, _C._ptr(pts), ctypes.c_int(pts.shape[0]), _C._ptr(q), ctypes.c_int(nq),
+        rc = _C.lib().gsr_knn(ws.fn, None, _C._ptr(pts), ctypes.c_int(pts.shape[0]), qptr, ctypes.c_int(nq),
                               ctypes.c_int(k), _C._ptr(dist2), _C._ptr(idx), _C._stream(pts.device))
-    if rc == -2:
-        raise ValueError("knn: a point coordinate is not finite")
-    _rc("gsr_knn", rc)
+    _rc("knn", rc)
     return dist2, idx
 
 
@@ -238,9 +248,7 @@ def statistical_outlier_mask(points, nb_neighbors=50, std_ratio=2.0, return_dist
             rc = _C.lib().gsr_outlier_statistical(ws.fn, None, _C._ptr(pts), ctypes.c_int(n), ctypes.c_int(nb_neighbors),
                                                   ctypes.c_double(std_ratio), _C._ptr(keep), _C._ptr(dist),
                                                   _C._stream(pts.device))
-        if rc == -2:
-            raise ValueError("statistical_outlier_mask: a point coordinate is not finite")
-        _rc("gsr_outlier_statistical", rc)
+        _rc("statistical_outlier_mask", rc)
     return (keep.bool(), dist) if return_distances else keep.bool()
 
 
@@ -264,9 +272,7 @@ def normal_outlier_mask(points, normals, nb_neighbors=20, angle_threshold=math.p
             rc = _C.lib().gsr_outlier_normal(ws.fn, None, _C._ptr(pts), _C._ptr(nrm), ctypes.c_int(n),
                                              ctypes.c_int(nb_neighbors), ctypes.c_double(angle_threshold), _C._ptr(keep),
                                              _C._stream(pts.device))
-        if rc == -2:
-            raise ValueError("normal_outlier_mask: a point coordinate is not finite")
-        _rc("gsr_outlier_normal", rc)
+        _rc("normal_outlier_mask", rc)
     return keep.bool()
 
 

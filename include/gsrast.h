@@ -39,6 +39,8 @@ extern "C" {
 #define GSR_ERR_ARG (-2)         /* invalid argument (e.g. neither SH nor colours; rasterizer_impl.cu:245-248) */
 #define GSR_ERR_PREFILTERED (-3) /* a point was culled although `prefiltered` is set (auxiliary.h:156-160) */
 #define GSR_ERR_ALLOC (-4)       /* an allocator callback returned NULL */
+#define GSR_ERR_NONFINITE (-5)   /* gsr_knn, gsr_fusion_smooth, gsr_outlier_*: a point coordinate is not finite */
+#define GSR_ERR_NONFINITE_QUERY (-6) /* gsr_knn: a query coordinate is not finite */
 
 /* Replaces std::function<char*(size_t)> (rasterizer.h:38-40): must return device memory of at
  * least `bytes` bytes, 256-byte aligned, that stays valid until the matching backward has run.
@@ -538,7 +540,10 @@ int gsr_surfel_backward(const gsr_options* opt, int P, int D, int M, int R, int 
  * ignored) the k nearest of points[num_points,3] (f32, all finite), 1 <= k <= min(64, num_points), in ascending
  * (squared distance, index) order: dist2[num_queries,k] (f64, computed from the f32 coordinates) and indices[num_queries,k]
  * (i64).  A query point that is also a data point finds itself first unless a duplicate with a lower index ties with it.
- * GSR_ERR_ARG for a bad k or a non-finite point coordinate. */
+ * Every tie is broken by the index, so the output is fully determined.  num_queries = 0 with non-NULL queries writes nothing
+ * (the grid is still built and the points are still checked).  GSR_ERR_ARG for a bad k or a NULL pointer,
+ * GSR_ERR_NONFINITE for a point and GSR_ERR_NONFINITE_QUERY for a query coordinate that is NaN or infinite (the queries are
+ * checked on the device while they are answered; dist2 and indices are then unspecified). */
 int gsr_knn(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, const float* queries,
             int num_queries, int k, double* dist2, int64_t* indices, void* stream);
 

@@ -1,5 +1,6 @@
 """Float64 numpy / scipy restatement of gs-extract-pcd's normal fusion and point-cloud cleaning (the contract of
-INTEGRATION.md "gs-extract-pcd"; extract_pcd.py:30-51 and :108-183).  kNN from scipy.spatial.cKDTree.  CPU only."""
+INTEGRATION.md "gs-extract-pcd"; extract_pcd.py:30-51 and :108-183).  kNN from scipy.spatial.cKDTree by default, or from
+knn_exact (brute force, ties broken by the index) through the `knn=` argument.  CPU only."""
 import numpy as np
 from scipy.spatial import cKDTree
 
@@ -17,6 +18,34 @@ def knn(points, k, queries=None):
     d, i = cKDTree(p).query(q, k=k)
     d, i = d.reshape(len(q), k), i.reshape(len(q), k)
     return d * d, i
+
+
+def knn_exact(points, k, queries=None):
+    """(dist2 [Q,k] float64, idx [Q,k] int64) by brute force, in ascending (dist2, index) order: the fully determined
+    result that include/gsrast.h promises of gsr_knn.  dist2 = dx*dx + dy*dy + dz*dz in float64 from the float32 values
+    of the coordinates, summed in that order.  Chunked over the queries (about 2^22 distances at a time)."""
+    p = np.asarray(points).astype(np.float32).astype(np.float64).reshape(-1, 3)
+    q = p if queries is None else np.asarray(queries).astype(np.float32).astype(np.float64).reshape(-1, 3)
+    n = len(p)
+    if not 1 <= k <= n:
+        raise ValueError(f"k = {k} needs 1 <= k <= {n} points")
+    dist2 = np.empty((len(q), k), dtype=np.float64)
+    idx = np.empty((len(q), k), dtype=np.int64)
+    step = max(1, (1 << 22) // n)
+    for b in range(0, len(q), step):
+        d = p[None, :, :] - q[b:b + step, None, :]
+        d2 = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
+        # every entry up to the k-th distance, ties included, then ordered by (row, dist2, index); the first k of a row
+        kth = np.partition(d2, k - 1, axis=1)[:, k - 1:k]
+        r, c = np.nonzero(d2 <= kth)
+        v = d2[r, c]
+        o = np.lexsort((c, v, r))
+        r, c, v = r[o], c[o], v[o]
+        first = np.searchsorted(r, np.arange(d2.shape[0]))
+        keep = np.arange(len(r)) - first[r] < k
+        dist2[b:b + step] = v[keep].reshape(-1, k)
+        idx[b:b + step] = c[keep].reshape(-1, k)
+    return dist2, idx
 
 
 def record_weights(xyz, ids, normals, conf, t):
@@ -55,8 +84,9 @@ def fused_means(xyz, ids_list, normals_list, conf_list, translations, consistenc
     return uids, m1, m2, {"record_diff": diff, "sum_ratio": ratio, "inverse": inv}
 
 
-def normal_fusion(xyz, ids_list, normals_list, conf_list, translations, k=10, sigma=0.1, consistency=0.8):
-    """-> (unique_ids int64 [U], normals float64 [U,3])."""
+def normal_fusion(xyz, ids_list, normals_list, conf_list, translations, k=10, sigma=0.1, consistency=0.8, knn=knn):
+    """-> (unique_ids int64 [U], normals float64 [U,3]).  knn: the neighbour search of this and of the functions below
+    (points, k) -> (dist2, idx); cKDTree unless given."""
     uids, _, m2, _ = fused_means(xyz, ids_list, normals_list, conf_list, translations, consistency)
     if len(uids) < k:
         raise ValueError("fewer fused points than k")
@@ -67,7 +97,7 @@ def normal_fusion(xyz, ids_list, normals_list, conf_list, translations, k=10, si
     return uids, _normalize(s)
 
 
-def statistical_outlier_mask(points, nb_neighbors=50, std_ratio=2.0):
+def statistical_outlier_mask(points, nb_neighbors=50, std_ratio=2.0, knn=knn):
     """-> (keep bool [N], a [N], threshold)."""
     p = np.asarray(points, dtype=np.float64)
     k = min(nb_neighbors, len(p))
@@ -81,7 +111,7 @@ def statistical_outlier_mask(points, nb_neighbors=50, std_ratio=2.0):
     return (a > 0) & (a < thr), a, thr
 
 
-def normal_outlier_mask(points, normals, nb_neighbors=20, angle_threshold=np.pi / 4):
+def normal_outlier_mask(points, normals, nb_neighbors=20, angle_threshold=np.pi / 4, knn=knn):
     """-> (keep bool [N], mean angle [N])."""
     p = np.asarray(points, dtype=np.float64)
     n = np.asarray(normals, dtype=np.float64)
@@ -93,13 +123,13 @@ def normal_outlier_mask(points, normals, nb_neighbors=20, angle_threshold=np.pi 
     return ang < angle_threshold, ang
 
 
-def clean_point_cloud(points, normals, nb_neighbors=50, std_ratio=2.0, normal_neighbors=20, angle_threshold=np.pi / 4):
+def clean_point_cloud(points, normals, nb_neighbors=50, std_ratio=2.0, normal_neighbors=20, angle_threshold=np.pi / 4, knn=knn):
     """-> ascending kept indices."""
-    keep1, _, _ = statistical_outlier_mask(points, nb_neighbors, std_ratio)
+    keep1, _, _ = statistical_outlier_mask(points, nb_neighbors, std_ratio, knn)
     first = np.nonzero(keep1)[0]
     if len(first) == 0:
         return first
-    keep2, _ = normal_outlier_mask(np.asarray(points)[first], np.asarray(normals)[first], normal_neighbors, angle_threshold)
+    keep2, _ = normal_outlier_mask(np.asarray(points)[first], np.asarray(normals)[first], normal_neighbors, angle_threshold, knn)
     return first[keep2]
 
 

@@ -1,6 +1,8 @@
 """gs-extract-pcd on the GPU (gaustudio_amd.pcd_fusion over csrc/gsr_knn.hip): exact kNN against scipy's cKDTree,
 normal fusion against the reference's own output (tests/golden/py_pcd_fusion.npz) and the float64 model, run-to-run
-bit-identity, the outlier masks against the model, and the whole per-view chain on frames rendered by the operator."""
+bit-identity, the grouping's edges (radix passes, sort tiles, the record buffer's growth, degenerate ids, record order),
+the outlier masks against the model, and the whole per-view chain on frames rendered by the operator.  The kNN's and the
+masks' edge cases, compared exactly: tests/test_gpu_knn_edges.py."""
 import math
 import os
 import sys
@@ -102,16 +104,16 @@ def test_knn_rejects_non_finite_points():
 
 
 # ------------------------------------------------------------------------------------------------------------ fusion
-def run_gpu_fusion(c, k=10):
+def run_gpu_fusion(c, k=10, consistency=0.8):
     xyz = torch.from_numpy(c["xyz"]).to(DEV)
     return pcd().normal_fusion(xyz, [torch.from_numpy(i).to(DEV) for i in c["ids"]],
                                [torch.from_numpy(n).to(DEV) for n in c["normals"]],
-                               [torch.from_numpy(f).to(DEV) for f in c["conf"]], c["t"], k=k)
+                               [torch.from_numpy(f).to(DEV) for f in c["conf"]], c["t"], k=k, consistency=consistency)
 
 
-def events(c, consistency=0.8):
+def events(c, consistency=0.8, knn=model.knn, k=10):
     """Unique ids whose fused normal may legitimately differ from a float32 / float64 restatement by more than the
-    tolerance, and every fused point that has one of them among its 10 smoothing neighbours:
+    tolerance, and every fused point that has one of them among its k (10) smoothing neighbours:
       * a record within 1e-5 of the 0.8 consistency threshold (the record is in or out depending on rounding);
       * an id whose consistent records nearly cancel, |S| / W < 1e-3 (normalising amplifies the rounding)."""
     uids, _, _, st = model.fused_means(c["xyz"], c["ids"], c["normals"], c["conf"], c["t"], consistency)
@@ -119,7 +121,7 @@ def events(c, consistency=0.8):
     near = np.abs(st["record_diff"] - consistency) < 1e-5
     flagged[st["inverse"][near]] = True
     flagged |= st["sum_ratio"] < 1e-3
-    _, nbr = model.knn(c["xyz"].astype(np.float64)[uids], 10)
+    _, nbr = knn(c["xyz"].astype(np.float64)[uids], k)
     return flagged[nbr].any(axis=1)
 
 
@@ -181,6 +183,152 @@ def test_fusion_errors():
     f.add_view(torch.tensor([100], device=DEV, dtype=torch.int32), torch.rand(1, 3, device=DEV), torch.ones(1, device=DEV), [3, 0, 0])
     with pytest.raises(ValueError, match="outside"):
         f.finalize(k=2)
+
+
+# ------------------------------------------------------------------------------------------- fusion: grouping edges
+def small_case(P, counts, seed, distinct=400, int64=False):
+    """`counts` records per view over at most `distinct` ids of [0, P), ids 0 and P - 1 among them, and 20 ids with a
+    single record; every id has a direction of its own, its records scatter around it (a few far enough to fail the
+    consistency test)."""
+    rng = np.random.default_rng(seed)
+    xyz = rng.uniform(-1, 1, size=(P, 3)).astype(np.float32)
+    pool = np.unique(np.concatenate([[0, P - 1], rng.integers(0, P, size=min(distinct, P))]))
+    singles = rng.permutation(np.setdiff1d(np.arange(min(P, 1 << 17)), pool))[:20]     # ids with exactly one record
+    axis = rng.normal(size=(P, 3)) if P <= 1 << 12 else None
+    ids, nrm, conf, t = [], [], [], []
+    for v, m in enumerate(counts):
+        i = rng.choice(pool, size=m)
+        if v == 0:                                                     # every id of the pool at least once
+            first = np.concatenate([rng.permutation(pool), singles])[:m]
+            i[:len(first)] = first
+            i = rng.permutation(i)
+        base = axis[i] if axis is not None else np.stack([np.sin(i * 0.7), np.cos(i * 1.3), np.sin(i * 0.37 + 1)], axis=1)
+        n = base / np.linalg.norm(base, axis=1, keepdims=True) + 0.25 * rng.normal(size=(m, 3))
+        wild = rng.uniform(size=m) < 0.05
+        n[wild] = rng.normal(size=(int(wild.sum()), 3))
+        ids.append(i.astype(np.int64 if int64 else np.int32))
+        nrm.append((n / np.linalg.norm(n, axis=1, keepdims=True)).astype(np.float32))
+        conf.append(rng.uniform(0.5, 1.0, size=m).astype(np.float32))
+        t.append(np.array([3.0 * math.cos(v), 0.5, 3.0 * math.sin(v)], dtype=np.float32))
+    return dict(xyz=xyz, ids=ids, normals=nrm, conf=conf, t=t)
+
+
+def check_small_case(c, k=10):
+    uids, normals = run_gpu_fusion(c, k=k)
+    ref_u, ref_n = model.normal_fusion(c["xyz"], c["ids"], c["normals"], c["conf"], c["t"], k=k, knn=model.knn_exact)
+    compare_fused(uids, normals, ref_u, ref_n, events(c, knn=model.knn_exact, k=k))
+    return uids, normals, ref_n
+
+
+# the radix sort runs ceil(bits(num_gaussians - 1) / 8) passes over 4096-key tiles: both sides of 2^8 and 2^16 Gaussians,
+# and of one tile of records
+@pytest.mark.parametrize("P,records,k", [(2, 300, 2), (256, 4095, 10), (257, 4096, 10), (65536, 4097, 10), (65537, 4096, 10),
+                                         (257, 1, 1)])
+def test_fusion_grouping_sizes(P, records, k):
+    c = small_case(P, [records], seed=P + records + (1000 if P == 257 and records == 4096 else 0))   # seeds without events
+    uids, _, _ = check_small_case(c, k)
+    u = uids.cpu().numpy()
+    if records > 1:
+        assert u[0] == 0 and u[-1] == P - 1
+    counts = np.bincount(c["ids"][0], minlength=P)
+    assert records == 1 or P == 2 or ((counts == 1).any() and (counts > 8).any()), "ids with one record and with many"
+
+
+def test_fusion_record_buffer_grows_across_views():
+    """Three views carry the record buffer across its first 65536 records (and the second one across a tile edge), with
+    int64 ids."""
+    c = small_case(5000, [40000, 25536 + 1, 30000], seed=3, distinct=1500, int64=True)
+    f = pcd().NormalFusion(torch.from_numpy(c["xyz"]).to(DEV))
+    sizes = []
+    for i, n, w, t in zip(c["ids"], c["normals"], c["conf"], c["t"]):
+        f.add_view(torch.from_numpy(i).to(DEV), torch.from_numpy(n).to(DEV), torch.from_numpy(w).to(DEV), t)
+        sizes.append(f.records.shape[0])
+    assert sizes[0] == 1 << 16 and sizes[1] > 1 << 16 and f.num_records == 95537
+    uids, normals = f.finalize()
+    ref_u, ref_n = model.normal_fusion(c["xyz"], c["ids"], c["normals"], c["conf"], c["t"], knn=model.knn_exact)
+    compare_fused(uids, normals, ref_u, ref_n, events(c, knn=model.knn_exact))
+    assert uids.dtype == torch.int32
+
+
+def test_fusion_degenerate_ids_poison_their_neighbours_only():
+    """An id whose weights are all zero (0 / 0 in the first mean) and an id with two opposite normals of equal weight
+    (mean 0, no record within 0.8 of it) fuse to NaN; the smoothing spreads the NaN to exactly the points that have
+    one of them among their 10 nearest, as the model says."""
+    c = small_case(3000, [4000, 3000], seed=5, distinct=600)
+    pool = np.unique(np.concatenate(c["ids"]))
+    zero_w, opposite = int(pool[len(pool) // 3]), int(pool[2 * len(pool) // 3])
+    for v in range(2):
+        c["conf"][v][c["ids"][v] == zero_w] = 0.0
+        keep = c["ids"][v] != opposite
+        c["ids"][v], c["normals"][v], c["conf"][v] = c["ids"][v][keep], c["normals"][v][keep], c["conf"][v][keep]
+    n = np.array([[0.6, 0.0, 0.8]], dtype=np.float32)
+    c["ids"][1] = np.concatenate([c["ids"][1][:1000], [opposite], c["ids"][1][1000:], [opposite]]).astype(np.int32)
+    c["normals"][1] = np.concatenate([c["normals"][1][:1000], n, c["normals"][1][1000:], -n])
+    c["conf"][1] = np.concatenate([c["conf"][1][:1000], [0.75], c["conf"][1][1000:], [0.75]]).astype(np.float32)
+    uids, normals, ref_n = check_small_case(c)              # compare_fused: NaN in the same places
+    u = uids.cpu().numpy()
+    nan = np.isnan(normals.cpu().numpy()).any(axis=1)
+    sources = np.isin(u, [zero_w, opposite])
+    _, nbr = model.knn_exact(c["xyz"][u], 10)
+    assert sources.sum() == 2 and nan[sources].all()
+    assert np.array_equal(nan, sources[nbr].any(axis=1)) and 2 < nan.sum() <= 40
+    assert np.array_equal(nan, np.isnan(ref_n).any(axis=1))
+
+
+def sequential_fusion(records, consistency):
+    """extract_pcd.py:130-181 for one id at k = 1, its records [(normal, weight)] summed one after the other in float64
+    (the 1e-12 floor under both means' norms included: with weights of 2^60 it is what the means are divided by)."""
+    def mean(rs):
+        s, w = np.zeros(3), 0.0
+        for n, wt in rs:
+            s = s + np.asarray(n, dtype=np.float64) * wt
+            w = w + wt
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = s / w
+        return m / max(math.sqrt(float((m * m).sum())), 1e-12)
+    m1 = mean(records)
+    m2 = mean([(n, w) for n, w in records if math.sqrt(float(((np.asarray(n, dtype=np.float64) - m1) ** 2).sum())) < consistency])
+    f = m2.astype(np.float32)                                # k = 1 smoothing: the mean itself, F.normalize in float32
+    return f / max(np.sqrt((f * f).sum(dtype=np.float32)), np.float32(1e-12))
+
+
+@pytest.mark.parametrize("order", [(0, 1, 2, 3), (0, 2, 1, 3), (1, 0, 2, 3), (3, 2, 1, 0), (2, 3, 0, 1)])
+def test_fusion_sums_an_ids_records_in_record_order(order):
+    """The stable sort, observed: four records of one id whose float64 sum depends on the order (2^60 + 1 - 2^60 is 0 or
+    1), spread over four 4096-key tiles among 13000 records of other ids.  In the order r1 r2 r3 r4 the x-sum is exactly
+    0 and the result (0, 1, 0); with r2 after r3 it is (0.707, 0.707, 0)."""
+    big = 2.0 ** 60
+    four = [((1.0, 0.0, 0.0), big), ((1.0, 0.0, 0.0), 1.0), ((-1.0, 0.0, 0.0), big), ((0.0, 1.0, 0.0), 1.0)]
+    four = [four[j] for j in order]
+    rng = np.random.default_rng(8)
+    P, special, n = 1000, 517, 13000
+    ids = rng.integers(0, P, size=n).astype(np.int32)
+    ids[ids == special] = special + 1
+    nrm = rng.normal(size=(n, 3))
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(np.float32)
+    w = rng.uniform(0.1, 1.0, size=n).astype(np.float32)
+    at = [5, 4100, 8200, 12300]                              # one position in each of the four tiles
+    for pos, (normal, weight) in zip(at, four):
+        ids[pos], nrm[pos], w[pos] = special, normal, weight
+    rec = np.empty((n, 5), dtype=np.int32)
+    rec[:, 0] = ids
+    rec[:, 1:4] = nrm.view(np.int32)
+    rec[:, 4] = w.view(np.int32)
+    f = pcd().NormalFusion(torch.from_numpy(rng.uniform(size=(P, 3)).astype(np.float32)).to(DEV))
+    f.records[:n] = torch.from_numpy(rec).to(DEV)
+    f.num_records = n
+    uids, normals = f.finalize(k=1, consistency=10.0)       # k = 1: the smoothing returns the id's own mean
+    u = uids.cpu().numpy()
+    assert np.array_equal(u, np.unique(ids))
+    got = normals.cpu().numpy()
+    expect = sequential_fusion(four, 10.0)
+    assert np.abs(expect).max() > 0.7 and (order != (0, 1, 2, 3) or np.array_equal(expect, [0.0, 1.0, 0.0]))
+    # float32 output of a float64 computation: 2^-24 relative per component, twice (mean, then the smoothing's normalize)
+    assert np.abs(got[u == special][0] - expect).max() <= 4 * 2.0 ** -24, (got[u == special][0], expect)
+    for j in (0, 1, len(u) - 1):                             # and three other ids, their records in record order as well
+        sel = ids == u[j]
+        e = sequential_fusion(list(zip(nrm[sel].astype(np.float64), w[sel].astype(np.float64))), 10.0)
+        assert np.abs(got[j] - e).max() <= 4 * 2.0 ** -24
 
 
 # ------------------------------------------------------------------------------------------------------------ cleaning

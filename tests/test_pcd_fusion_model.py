@@ -1,5 +1,7 @@
-"""gs-extract-pcd normal fusion / cleaning: the float64 model against the reference's own normal_fusion (fixture), and
-the argument checks of gaustudio_amd.pcd_fusion that need no device."""
+"""gs-extract-pcd normal fusion / cleaning: the float64 model against the reference's own normal_fusion (fixture), the
+exact (dist2, index)-ordered kNN of the model against cKDTree, the small cleaning inputs of the GPU edge tests (none may
+sit at a threshold), and the argument checks of gaustudio_amd.pcd_fusion that need no device."""
+import functools
 import math
 import os
 import sys
@@ -9,6 +11,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import pcd_edge_cases as edge  # noqa: E402
 import pcd_fusion_model as model  # noqa: E402
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "py_pcd_fusion.npz")
@@ -64,6 +67,113 @@ def test_open3d_statistical_parity():
     _, ind = pc.remove_statistical_outlier(nb_neighbors=50, std_ratio=2.0)
     keep, _, _ = model.statistical_outlier_mask(p)
     assert np.array_equal(np.nonzero(keep)[0], np.asarray(ind))
+
+
+# ---------------------------------------------------------------------------------------------------- the exact kNN
+@pytest.mark.parametrize("k", [1, 10, 64])
+def test_knn_exact_equals_ckdtree_without_ties(k):
+    rng = np.random.default_rng(k)
+    p = rng.uniform(-1, 1, size=(3000, 3)).astype(np.float32)
+    q = rng.uniform(-1.5, 1.5, size=(700, 3)).astype(np.float32)
+    for queries in (None, q):
+        d2, idx = model.knn_exact(p, k, queries)
+        rd2, ridx = model.knn(p, k, queries)
+        assert d2.dtype == np.float64 and idx.dtype == np.int64 and d2.shape == idx.shape == (len(rd2), k)
+        assert (np.diff(d2, axis=1) > 0).all(), "the cloud was meant to be tie-free"
+        assert np.array_equal(idx, ridx)
+        assert np.all(np.abs(d2 - rd2) <= 1e-14 * rd2)      # cKDTree squares a rounded square root
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_reference():
+    return model.knn_exact(edge.cloud("lattice"), 64)
+
+
+@pytest.mark.parametrize("k", [1, 10, 20, 50, 64])
+def test_knn_exact_orders_lattice_ties_by_index(k):
+    p = edge.cloud("lattice")
+    d2, idx = model.knn_exact(p, k)
+    d64, idx64 = lattice_reference()
+    assert np.array_equal(d2, d64[:, :k]) and np.array_equal(idx, idx64[:, :k]), "a smaller k is a prefix: the order is total"
+    rd2, ridx = model.knn(p, k)
+    assert np.array_equal(d2, np.round(rd2)), "integer squared distances: the k nearest distances are cKDTree's"
+    pd = p.astype(np.float64)
+    assert np.array_equal(d2, ((pd[idx] - pd[:, None, :]) ** 2).sum(axis=2))
+    lexicographic = (d2[:, 1:] > d2[:, :-1]) | ((d2[:, 1:] == d2[:, :-1]) & (idx[:, 1:] > idx[:, :-1]))
+    assert lexicographic.all()
+    # no lower index was passed over: every point tied with the k-th distance and left out has a higher index than
+    # every tied point that was taken
+    for i in range(0, len(p), 97):
+        full = ((pd - pd[i]) ** 2).sum(axis=1)
+        tied = np.nonzero(full == d2[i, -1])[0]
+        taken = idx[i][d2[i] == d2[i, -1]]
+        assert np.array_equal(taken, tied[:len(taken)])
+        assert (full < d2[i, -1]).sum() == (d2[i] < d2[i, -1]).sum()
+    if k >= 10:
+        assert not np.array_equal(np.sort(idx, axis=1), np.sort(ridx, axis=1)), "cKDTree's ties were meant to differ"
+
+
+def test_knn_exact_chunks_queries_and_rejects_bad_k():
+    p = edge.cloud("duplicates")
+    d2, idx = model.knn_exact(p, 10)                        # 4000 queries: several chunks
+    assert (d2 == 0).all()
+    groups = {}
+    for i, row in enumerate(map(bytes, p)):
+        groups.setdefault(row, []).append(i)
+    for i in (0, 1, 1234, 3999):
+        assert idx[i].tolist() == groups[bytes(p[i])][:10]  # the group's ten lowest indices, the query itself or not
+    with pytest.raises(ValueError):
+        model.knn_exact(p[:5], 6)
+    with pytest.raises(ValueError):
+        model.knn_exact(p, 0)
+
+
+# ------------------------------------------------------------------- the cleaning inputs of the GPU edge tests
+def cleaning_events(name, nb):
+    """Near-threshold events of the model (knn_exact) on one cleaning input, by the definitions of the large GPU tests:
+    |a - thr| <= 1e-9 thr in the statistical test, |angle - pi/4| <= 1e-9 pi/4 in the normal test, the latter on the whole
+    cloud and on what the statistical test kept (clean_point_cloud)."""
+    p, n = edge.cleaning_cloud(name)
+    keep, a, thr = model.statistical_outlier_mask(p, nb, 2.0, knn=model.knn_exact)
+    stat = int((np.abs(a - thr) <= 1e-9 * thr).sum())
+    _, ang = model.normal_outlier_mask(p, n, nb, knn=model.knn_exact)
+    near = int((np.abs(ang - math.pi / 4) <= 1e-9 * math.pi / 4).sum())
+    if keep.any():
+        _, ang = model.normal_outlier_mask(p[keep], n[keep], 20, knn=model.knn_exact)
+        near += int((np.abs(ang - math.pi / 4) <= 1e-9 * math.pi / 4).sum())
+    return stat, near, (keep, a, thr)
+
+
+@pytest.mark.parametrize("name,nb", edge.cleaning_inputs())
+def test_cleaning_edge_inputs_have_no_threshold_events(name, nb):
+    stat, near, (keep, a, thr) = cleaning_events(name, nb)
+    assert near == 0
+    if name == "n2" and nb >= 2:
+        # two points are each other's only neighbour: a_0 = a_1 = d / 2, their mean (a + a) / 2 = a and every deviation
+        # a - a = 0 without any rounding, so thr = a + 2 * 0 = a_i exactly and `a_i < thr` is false in any IEEE
+        # arithmetic.  The definition counts both points as events; nothing here depends on a rounding.
+        assert stat == 2 and a[0] == a[1] == thr and not keep.any()
+    else:
+        assert stat == 0
+
+
+def test_cleaning_edge_inputs_exercise_both_outcomes():
+    for name, nb in (("n255", 20), ("n256", 50), ("n257", 20), ("n513", 50)):
+        p, n = edge.cleaning_cloud(name)
+        keep, _, _ = model.statistical_outlier_mask(p, nb, knn=model.knn_exact)
+        assert 0 < keep.sum() < len(p)
+        keep, _ = model.normal_outlier_mask(p, n, nb, knn=model.knn_exact)
+        assert 0 < keep.sum() < len(p)
+    for name in ("identical", "pairs_and_one"):
+        p, _ = edge.cleaning_cloud(name)
+        keep, a, thr = model.statistical_outlier_mask(p, 2, knn=model.knn_exact)
+        assert not keep.any() and math.isnan(thr) and (a > 0).sum() == (name == "pairs_and_one")
+    p, n = edge.cleaning_cloud("duplicated_fifth")
+    _, idx = model.knn_exact(p, 20)
+    assert 150 <= (idx[:, 0] != np.arange(len(p))).sum() <= 200, "the higher index of a pair does not find itself first"
+    exact, _ = model.normal_outlier_mask(p, n, 20, knn=model.knn_exact)
+    assert 0 < exact.sum() < len(p)
+    assert not model.normal_outlier_mask(p, n, 1, knn=model.knn_exact)[0].any()      # k = 1: the mean of nothing
 
 
 # ---------------------------------------------------------------------------------- argument checks, no device needed

@@ -504,6 +504,10 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) void composite_bwd_kernel(
 //   flush phases: +-0.3 %) and a length-balanced assignment of the sixteen quarters to the four waves (census: -2.8 % wave-steps at
 //   C3, profiles/r06_quarter_balance_census.txt; profiles/r06_composite_bwd_experiments.txt).  profiles/r03_composite_bwd_phases.txt: a wave walks
 //   for 68 % of its life, and the walk is sensitive to VALU and LDS at once with neither saturated.
+//   Staging is software-pipelined across the walk: a round's records are requested while the round before it is walked, its
+//   ids a round earlier still, by unmasked loads whose values nothing touches until they are staged; one wait before the flush
+//   (see "software-pipelined staging" in the kernel).  Until round 8 the source said so and the ISA did not: a repack of the
+//   loaded words and exec-masked loads put s_waitcnt vmcnt(0) right behind each of the round's loads.
 // A wave walks max over its quarters (C3: 0.73x the steps of the 8x8 walk), and phase 2 touches only hit quarters.
 // The median-depth gradient (one Gaussian per pixel, the list position the forward recorded) is added once per pixel,
 // by an LDS atomic before the walk of the batch that position falls into.
@@ -515,6 +519,9 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) void composite_bwd_kernel(
 #define GSR_BWQ_HALVES ((GSR_BWQ_BATCH + 63) / 64)
 #define GSR_BWQ_LIST (GSR_BWQ_BATCH + 8)   // bytes per quarter list: the entries + 8 sentinels
 #define GSR_BWQ_SENT GSR_BWQ_BATCH         // batch index of the sentinel record (opacity 0)
+// s_waitcnt vmcnt(0) alone (expcnt 7, lgkmcnt 15 = no wait; gfx9 encoding): every outstanding global load has arrived.  As a builtin it
+// is seen by the compiler's own wait insertion, which counts from it
+#define GSR_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0F70)
 #define GSR_BWQ_QSTRIDE 66   // float2 per quarter in the slab: 4 steps x 16 pixels + 2 pad (16-B aligned, banks shifted)
 
 // FX: exp on the transcendental unit (gs_exp_hw), after a forward that ran in fast_exp mode: same instruction, same
@@ -569,8 +576,9 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 	const float fbx = (float)(tx * GSR_BLOCK_X + ((wv & 1) << 3)), fby = (float)(ty * GSR_BLOCK_Y + ((wv >> 1) << 3));
 	const uint2 range = ranges[tile];
 	// the forward's per-instance block masks (gs_qmask_ptr), if it left them: the cull below then costs two shifts
-	const bool have_qmask = ctl->has_qmask != 0u;
-	const uint16_t* __restrict__ qmask = gs_qmask_ptr(point_list, ctl->num_binned);
+	// (both words are the same for every lane; read as such they stay in scalar registers, and so does the pointer chosen by them below)
+	const bool have_qmask = __builtin_amdgcn_readfirstlane(ctl->has_qmask) != 0u;
+	const uint16_t* __restrict__ qmask = gs_qmask_ptr(point_list, __builtin_amdgcn_readfirstlane(ctl->num_binned));
 
 	const size_t sidx = (size_t)tile * GSR_TILE_PIX + (wv << 6) + ((ly & 7) << 3) + (lx & 7);   // tile-major pixel state
 	const float T_final = inside ? final_T[sidx] : 0.f;
@@ -617,6 +625,10 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			g_op[sx] = CONLY ? 0.f : tmp[2 * pl + 1].x;
 		}
 		__builtin_amdgcn_wave_barrier();
+		// the selections are finished here: left to itself the compiler sinks them (32 v_cndmask with sources and results
+		// alive at once) below the first records' loads, where registers are scarcest, and spills there
+#pragma unroll
+		for (int sx = 0; sx < 4; sx++) asm volatile("" : "+v"(g_pix[sx].x), "+v"(g_pix[sx].y), "+v"(g_pix[sx].z), "+v"(g_pix[sx].w));
 	}
 	const float y2 = fby + (float)(((qd >> 1) << 2) + r2), x2 = fbx + (float)((qd & 1) << 2);   // first pixel of that row
 	// bg . dL_dpixel (backward.cu:584-586), loop invariant
@@ -642,42 +654,62 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 	const int bmax = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
 	TM(1)
 
-	// rows of list entries no pixel of the tile reaches (short-list regime; see composite_bwd_kernel)
+	// ---- software-pipelined staging ----
+	// thread t fetches 16-B part (t & 3) of the records of staged instances (t >> 2) + 64 h, and one more word of the
+	// instance into the part's unused .w: the first row goff[id] (part 3: q3.w) or the forward's block mask (part 2: q2.w).
+	// What a round stages was requested a whole walk earlier: the round's loads -- both halves' record parts and words for
+	// round r + 1, the ids for round r + 2 -- are issued together as one straight-line sequence right after the staging, with
+	// nothing computed from them until the next staging (the words stay raw in part[]; the dead-corner bits and the mask's half
+	// word are taken there), and ONE wait in front of the flush, after the walk, makes them arrived: the flush's stores are
+	// issued behind it, and their acknowledgements drain under the next round's staging, zeroing and list building (a load
+	// wait on this target counts stores as well).  In the compiled kernel no s_waitcnt vmcnt stands between the round's first
+	// load and that wait (profiles/r08_composite_bwd_prefetch_isa.txt); it needs the kernel to be free of spills, whose reloads
+	// are counted with the loads (the two asm("") pins below and at g_pix are there for that).
+	// No lane is masked out of a load: a lane beyond the walk's end reads list position 0 of the tile (which exists wherever a
+	// walk does: 0 < bmax <= the list length) and the record that position names, and stages nothing (sr < cnt below).
+	const int srec = tid >> 2, spart = tid & 3;
+	const uint32_t* __restrict__ tile_list = point_list + range.x;
+	// block masks: two to an aligned 32-bit word (the mask array is 256-B aligned and lies in a region of at least 256 B).  A
+	// forward that left none (has_qmask == 0) has not written that memory: the list itself stands in, and nobody reads s_qmask
+	const uint32_t* __restrict__ mask_words = have_qmask ? reinterpret_cast<const uint32_t*>(qmask) : point_list;
+	auto list_pos = [&](int t, int h) -> uint32_t {   // position t-1-(srec + 64 h) of the tile's list, 0 when outside the walk
+		return (uint32_t)max(t - 1 - (srec + 64 * h), 0);
+	};
+	auto word_ptr = [&](int t, int h, uint32_t id) -> const uint32_t* {
+		return spart == 2 ? mask_words + ((range.x + list_pos(t, h)) >> 1) : goff + id;
+	};
+	uint32_t id_next[GSR_BWQ_HALVES];
+	float4 part[GSR_BWQ_HALVES];     // the round's record parts and words until they are staged, then the next round's
+#pragma unroll
+	for (int h = 0; h < GSR_BWQ_HALVES; h++) {
+		part[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+		id_next[h] = 0u;
+	}
+	if (bmax > 0) {   // (workgroup-uniform) two dependent latencies: the ids of the first two rounds, then the first round's records
+		uint32_t id_cur[GSR_BWQ_HALVES];
+#pragma unroll
+		for (int h = 0; h < GSR_BWQ_HALVES; h++) {
+			id_cur[h] = tile_list[list_pos(bmax, h)];
+			id_next[h] = tile_list[list_pos(bmax - GSR_BWQ_BATCH, h)];
+		}
+#pragma unroll
+		for (int h = 0; h < GSR_BWQ_HALVES; h++) {
+			part[h] = reinterpret_cast<const float4*>(recs + id_cur[h])[spart];
+			if (spart >= 2) part[h].w = __uint_as_float(*word_ptr(bmax, h, id_cur[h]));
+		}
+	}
+	// rows of list entries no pixel of the tile reaches (short-list regime; see composite_bwd_kernel): their dependent chain
+	// (id -> record, first row -> stores) runs under the staging chain requested above
 	for (int i = bmax + tid; !FLAGS && i < (int)(range.y - range.x); i += GSR_BWD_THREADS) {
-		const uint32_t id = point_list[range.x + i];
+		const uint32_t id = tile_list[i];
 		const uint4 q3 = recs[id].q3;
 		float4* dst = reinterpret_cast<float4*>(rows + (size_t)(goff[id] + gs_row_in_rect(q3.x, q3.y, (q3.z >> GSR_Q3Z_DEAD_SHIFT) & 15u, tx, ty)) * GSR_ROW_STRIDE);
 		dst[0] = make_float4(0.f, 0.f, 0.f, 0.f);
 		dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
 		dst[2] = make_float4(0.f, 0.f, 0.f, 0.f);
 	}
+	GSR_WAIT_VM0();   // the first round stages at once; and the round loop is entered, as it is re-entered, with no load in flight
 	TM(2)
-	// ---- software-pipelined staging (as in composite_bwd_kernel) ----
-	// thread t fetches 16-B part (t & 3) of the records of staged instances (t >> 2) + 64 h
-	const int srec = tid >> 2, spart = tid & 3;
-	auto load_id = [&](int t, int h) -> uint32_t {   // id of list position t-1-(srec + 64 h) (0 when outside the walk)
-		const int sr = srec + 64 * h;
-		return (t > 0 && sr < min(GSR_BWQ_BATCH, t)) ? point_list[range.x + (uint32_t)(t - 1 - sr)] : 0u;
-	};
-	auto load_part = [&](int t, int h, uint32_t id) -> float4 {
-		float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-		if (t > 0 && srec + 64 * h < min(GSR_BWQ_BATCH, t)) {
-			v = reinterpret_cast<const float4*>(recs + id)[spart];
-			if (spart == 3) {   // q3 = {rect min, rect max, clamp bits | dead corners, tiles}: .w <- first row, .z <- dead corners << 16 | the forward's block mask
-				v.w = __uint_as_float(goff[id]);
-				const uint32_t dead = (__float_as_uint(v.z) >> GSR_Q3Z_DEAD_SHIFT) & 15u;
-				v.z = __uint_as_float((dead << 16) | (have_qmask ? (uint32_t)qmask[range.x + (uint32_t)(t - 1 - (srec + 64 * h))] : 0u));
-			}
-		}
-		return v;
-	};
-	uint32_t id_next[GSR_BWQ_HALVES];
-	float4 part_cur[GSR_BWQ_HALVES];
-#pragma unroll
-	for (int h = 0; h < GSR_BWQ_HALVES; h++) {
-		id_next[h] = load_id(bmax - GSR_BWQ_BATCH, h);
-		part_cur[h] = load_part(bmax, h, load_id(bmax, h));
-	}
 	const uint8_t* my_list = &s_list[wv][qd][0];
 	const char* recA = reinterpret_cast<const char*>(sA);
 	const char* recB = reinterpret_cast<const char*>(sB);
@@ -694,29 +726,35 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 		for (int h = 0; h < GSR_BWQ_HALVES; h++) {
 			const int sr = srec + 64 * h;
 			if (sr < cnt) {
-				if (spart == 0) sA[sr] = part_cur[h];
-				else if (spart == 1) sB[sr] = part_cur[h];
-				else if (spart == 2) sC[sr] = part_cur[h];
-				else {
-					const uint32_t q3x = __float_as_uint(part_cur[h].x), q3y = __float_as_uint(part_cur[h].y), q3w = __float_as_uint(part_cur[h].w);
-					const uint32_t q3z = __float_as_uint(part_cur[h].z);
-					s_row[sr] = q3w + gs_row_in_rect(q3x, q3y, (q3z >> 16) & 15u, tx, ty);
-					s_qmask[sr] = (uint16_t)q3z;
+				if (spart == 0) sA[sr] = part[h];
+				else if (spart == 1) sB[sr] = part[h];
+				else if (spart == 2) {
+					sC[sr] = part[h];
+					s_qmask[sr] = (uint16_t)(__float_as_uint(part[h].w) >> (16u * ((range.x + (uint32_t)(top - 1 - sr)) & 1u)));
+				} else {   // q3 = {rect min, rect max, clamp bits | dead corners, tiles}
+					const uint32_t q3x = __float_as_uint(part[h].x), q3y = __float_as_uint(part[h].y), q3z = __float_as_uint(part[h].z);
+					s_row[sr] = __float_as_uint(part[h].w) + gs_row_in_rect(q3x, q3y, (q3z >> GSR_Q3Z_DEAD_SHIFT) & 15u, tx, ty);
 				}
 			}
 		}
 		TM(5)
-		float4 part_next[GSR_BWQ_HALVES];
+		// the next round's records and words, the ids of the round after it (one straight-line sequence, no lane masked out: above)
 #pragma unroll
 		for (int h = 0; h < GSR_BWQ_HALVES; h++) {
-			part_next[h] = load_part(top - GSR_BWQ_BATCH, h, id_next[h]);
-			id_next[h] = load_id(top - 2 * GSR_BWQ_BATCH, h);
+			part[h] = reinterpret_cast<const float4*>(recs + id_next[h])[spart];
+			if (spart >= 2) part[h].w = __uint_as_float(*word_ptr(top - GSR_BWQ_BATCH, h, id_next[h]));
 		}
+#pragma unroll
+		for (int h = 0; h < GSR_BWQ_HALVES; h++) id_next[h] = tile_list[list_pos(top - 2 * GSR_BWQ_BATCH, h)];
+		// (the two constants are made here, opaque to the compiler: as loop invariants it keeps them -- eight registers
+		// of a 128-bit zero and a 128-bit sentinel word -- alive across the walk, which the prefetched records then pay for in spills)
+		float zero = 0.f;
+		uint32_t ss = GSR_BWQ_SENT * 0x01010101u;
+		asm volatile("" : "+v"(zero), "+v"(ss));
 		for (int i = tid; i < 4 * GSR_BWQ_BATCH * GSR_PLANE_STRIDE / 4; i += GSR_BWD_THREADS)
-			reinterpret_cast<float4*>(&s_plane[0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+			reinterpret_cast<float4*>(&s_plane[0][0])[i] = make_float4(zero, zero, zero, zero);
 		// this wave's four lists: sentinels, then (below) the hits of each quarter in list order
 		if (lane < 4 * GSR_BWQ_LIST / 16) {
-			const uint32_t ss = GSR_BWQ_SENT * 0x01010101u;
 			reinterpret_cast<uint4*>(&s_list[wv][0][0])[lane] = make_uint4(ss, ss, ss, ss);
 		}
 		TM(6)
@@ -898,6 +936,7 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 		}
 		// flush: one thread per staged instance adds the four planes in fixed order and stores the 48-B row
 		TM(9)
+		GSR_WAIT_VM0();   // the loads requested at the top of the round have had the whole walk: arrived before the row stores are issued
 		__syncthreads();
 		TM(10)
 		for (int fj = tid; fj < cnt; fj += GSR_BWD_THREADS) {
@@ -918,8 +957,6 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			dst[2] = make_float4(v[6], v[7], 0.f, 0.f);
 			if (FLAGS) row_flags[my_row] = 1;
 		}
-#pragma unroll
-		for (int h = 0; h < GSR_BWQ_HALVES; h++) part_cur[h] = part_next[h];
 		TM(11)
 	}
 	TM_END

@@ -31,8 +31,10 @@ print("ms per fwd+bwd step", e0.elapsed_time(e1) / N)
 assert lib.gsr_debug_bwd_phase_ticks(buf, 0) == 0
 a = np.frombuffer(buf, dtype=np.uint64).reshape(SL, 12).astype(np.float64) / N
 live = a.sum(1) > 0
-names = ["pixel state arrives", "first barrier (bmax)", "zero-rows loop", "(first ids arrive / loop tail -> top)", "wait top-of-round barrier", "staging LDS writes (wait records)",
-         "issue next loads + zero planes + list init", "wait second barrier", "median + list building", "walk", "wait before flush", "flush"]
+# (until round 7 the first ids and records were requested BEHIND the zero-rows loop: phase 2 was that loop alone, phase 3 also held the
+# first ids' latency and phase 5 the wait for the records; since round 8 the one wait for a round's loads stands in phase 10)
+names = ["pixel state arrives", "first barrier (bmax)", "first ids + records requested, zero-rows loop, records arrive", "(loop tail -> top)", "wait top-of-round barrier", "staging LDS writes",
+         "issue next loads + zero planes + list init", "wait second barrier", "median + list building", "walk", "next round's loads arrived + wait before flush", "flush"]
 tot = a.sum()
 for k, n in enumerate(names):
     print(f"{n:45s} {a[:, k].sum():16.0f} {100.0 * a[:, k].sum() / tot:6.1f} %   per wave {a[live, k].mean():9.0f}")

@@ -153,7 +153,8 @@ def normalize_grid(grid, mean=None, scale=True, apply_tanh=False):
 
 class DPSR:
     """graphics_utils.DPSR(res, sig, scale, shift, weighted), forward only: `dpsr(V, N) -> phi`.  V, N: [N,3] float32 (V in
-    [0, 1)) -> phi [R0,R1,R2]; the reference's batched [1,N,3] -> [1,R0,R1,R2].  Batch size 1 only.  `apply_tanh=True` folds
+    [0, 1)) -> phi [R0,R1,R2]; the reference's batched [1,N,3] -> [1,R0,R1,R2].  Batch size 1 only, N >= 1 (ValueError for an
+    empty cloud, whatever the options).  `apply_tanh=True` folds
     the tanh that ShapeAsPoints.generate_mesh applies next into the normalisation pass.  The result has no grad_fn: gradients
     are out of scope."""
 
@@ -174,6 +175,8 @@ class DPSR:
             V, N = V[0], N[0]
         V = _device_tensor("V", V, 3)
         N = _device_tensor("N", N, 3)
+        if V.shape[0] < 1:
+            raise ValueError("DPSR needs at least one point")       # no samples to shift by, and 0 / 0 in the scaling
         _on_rocm(V=V, N=N)
         with torch.no_grad():
             ras = point_rasterize(V, N, self.res, weighted=self.weighted)

@@ -1,11 +1,13 @@
 """CPU model of gaustudio_amd.sap (csrc/gsr_psr.hip), written from the contract in INTEGRATION.md s17 -- not from the reference's
-program text.  numpy only.
+program text.  numpy only (dpsr32_cpu: scipy.fft, for an FFT that stays in single precision).
 
   * corners(): the per-axis index / weight arithmetic in float32, operation for operation as the contract states it;
   * rasterize(): per node the float32 terms w * val added in float64 (`sum64`), the pair count `k`, sum |term| (`abs64`);
   * interp(): the 8 float32 terms grid[corner] * w added in float64 in corner order;
   * spectral32(): the spectral solve in the device's float32 chain; dpsr64(): the whole solver in float64 (only the weights
-    stay float32), the yardstick E_ref is measured against;
+    stay float32), the yardstick E_ref is measured against; normalize32(): the float32 chain of normalize_grid;
+    dpsr32_cpu(): the whole solver in float32 on the CPU, whose distance from dpsr64 is E_ref where no fixture records one;
+  * near_node_coords(): the float32 coordinates beside the nodes of an axis, where the index chain can go wrong;
   * marching_cubes(): the dense indexed marching cubes with the derived tables of gaustudio_amd/csrc/gen_mc_tables.py.
 """
 import os
@@ -44,6 +46,21 @@ def valid(pts, size):
         with np.errstate(invalid="ignore"):
             ok &= ~(np.floor(pts[:, d] / (f32(1.0) / f32(size[d]))) >= size[d])
     return ok
+
+
+def near_node_coords(r):
+    """The float32 coordinates beside the nodes of an axis of r cells: float32(k / r) for k = 0 .. r and its three float32
+    neighbours on each side, those in [0, 1), ascending.  Where 1 / r is no float32 this set holds the coordinates whose
+    quotient p / cubesize rounds to an integer off the node, and (r = 100, 129) one below 1 whose quotient rounds up to r."""
+    c = (np.arange(r + 1, dtype=np.float64) / r).astype(f32)
+    out = [c]
+    lo, hi = c, c
+    for _ in range(3):
+        lo, hi = np.nextafter(lo, f32(-1)), np.nextafter(hi, f32(2))
+        out += [lo, hi]
+    out = np.unique(np.concatenate(out))
+    assert out.dtype == f32
+    return out[(out >= 0) & (out < 1)]
 
 
 def corners(pts, size):
@@ -166,6 +183,36 @@ def dpsr64(V, N, size, sig, scale=True, shift=True, weighted=False):
     if scale:
         phi = -phi / abs(phi[0, 0, 0]) * 0.5
     return phi
+
+
+def normalize32(grid, mean64=None, scale=True, shift=True):
+    """normalize_grid without the tanh, in the device's float32 chain (correctly rounded division, no contraction: bit for
+    bit): off = float32(mean64); v = grid - off; a = |v[0,0,0]|; (-v) / a * 0.5.  shift=False (or no mean): no offset."""
+    v = np.asarray(grid, f32)
+    if shift and mean64 is not None:
+        v = v - f32(np.float64(mean64))
+    if scale:
+        a = np.abs(v.reshape(-1)[0])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = (-v) / a * f32(0.5)
+    assert v.dtype == f32
+    return v
+
+
+def dpsr32_cpu(V, N, size, sig, scale=True, shift=True):
+    """The whole solver in float32 on the CPU: rasterize32 -> scipy rfftn (single precision) -> spectral32 -> scipy irfftn ->
+    the mean of the float32 samples -> normalize32.  Its distance from dpsr64 is E_ref of a shape without a recorded fixture:
+    the error of a float32 run of the same chain around a different float32 FFT than the device's."""
+    import scipy.fft
+    size = tuple(size)
+    ras, _ = rasterize32(V, N, size, False)
+    spec = scipy.fft.rfftn(ras, axes=(1, 2, 3))
+    assert spec.dtype == np.complex64, spec.dtype
+    Phi, _ = spectral32(spec, size, sig)
+    phi = scipy.fft.irfftn(Phi, s=size, axes=(0, 1, 2))
+    assert phi.dtype == f32, phi.dtype
+    mean = interp(phi, V)[0].astype(f32).astype(np.float64).mean() if shift else None
+    return normalize32(phi, mean, scale, shift)
 
 
 # ------------------------------------------------------------------------------------------------------ marching cubes

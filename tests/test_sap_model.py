@@ -67,6 +67,68 @@ def test_spectral32_follows_the_float64_solve(fx):
     assert np.abs(phi - ref).max() < 1e-5 * np.abs(ref).max()
 
 
+NO_REJECT = (2, 3, 5, 6, 7, 10, 12, 24, 36, 255, 256)
+ONE_REJECT = (100, 129)
+OFF_NODE_INTEGER = (7, 10, 12, 24, 36, 100, 255)
+
+
+@pytest.mark.parametrize("r", sorted(set(NO_REJECT + ONE_REJECT + OFF_NODE_INTEGER)))
+def test_near_node_coords_hold_the_edges(r):
+    """What tests/test_gpu_sap_edges.py relies on: the set holds the coordinate below 1 whose quotient rounds up to r (r = 100,
+    129) and coordinates whose quotient is an integer although the point is off the node."""
+    c = sm.near_node_coords(r)
+    assert c.dtype == np.float32 and (np.diff(c) > 0).all() and c[0] == 0 and c[-1] < 1
+    nodes = (np.arange(r, dtype=np.float64) / r).astype(np.float32)
+    assert np.isin(nodes, c).all() and np.isin(np.nextafter(nodes[1:], np.float32(0)), c).all()
+    assert np.float32(1 - 2.0 ** -24) in c
+    cs = np.float32(1.0) / np.float32(r)
+    q = c / cs
+    assert q.dtype == np.float32
+    rejected = np.floor(q) >= r
+    off_node = (q == np.floor(q)) & (np.floor(q) * cs != c)
+    print(f"r={r}: {len(c)} coordinates, {rejected.sum()} rejected, {off_node.sum()} with an integer quotient off the node")
+    assert rejected.sum() == (1 if r in ONE_REJECT else 0)
+    if r in OFF_NODE_INTEGER:
+        assert off_node.sum() >= 1
+    pts = np.zeros((len(c), 3), np.float32)
+    pts[:, 1] = c
+    assert np.array_equal(~sm.valid(pts, (2, r, 2)), rejected)
+    # every accepted coordinate indexes inside the grid, and its two weights are those of a point in or on the cell
+    (i0, i1), (w0, w1) = sm._axis(c[~rejected], r)
+    assert i0.min() >= 0 and i0.max() < r and i1.min() >= 0 and i1.max() < r
+    assert ((i1 == i0) | (i1 == (i0 + 1) % r)).all()
+    assert (w0 >= 0).all() and (w1 >= 0).all() and np.abs(w0.astype(np.float64) + w1 - 1).max() < 1e-4
+
+
+def test_normalize32_is_the_float32_chain():
+    rng = np.random.default_rng(5)
+    g = rng.normal(size=(5, 4, 3)).astype(np.float32)
+    m = 0.1234567890123
+    v = g.astype(np.float64) - float(np.float32(m))
+    want = -v / abs(v[0, 0, 0]) * 0.5
+    got = sm.normalize32(g, m)
+    assert got.dtype == np.float32 and got[0, 0, 0] == (-0.5 if v[0, 0, 0] > 0 else 0.5)
+    assert np.abs(got - want).max() <= 4 * sm.U * np.abs(want).max()
+    assert np.array_equal(sm.normalize32(g, m, scale=False), g - np.float32(m))
+    assert np.array_equal(sm.normalize32(g, None, scale=False), g) and np.array_equal(sm.normalize32(g, m, False, False), g)
+    assert np.array_equal(sm.normalize32(g, None), (-g) / np.abs(g[0, 0, 0]) * np.float32(0.5))
+    assert np.array_equal(sm.normalize32(g, m, shift=False), sm.normalize32(g, None))
+
+
+@pytest.mark.parametrize("res,n,measured", [((9, 7, 5), 3000, 1.7e-7), ((129, 129, 129), 70000, 5.4e-7)])
+def test_dpsr32_cpu_gives_eref(res, n, measured):
+    """E_ref of a shape without a recorded fixture: the float32 CPU run against the float64 model.  `measured` is the figure
+    of this chain with numpy 2.2.6 / scipy 1.15.3; another FFT build may move it, not its order."""
+    P, N = sm.ellipsoid_cloud(n, seed=1)
+    V = sm.unit_cube(P)[0]
+    phi = sm.dpsr32_cpu(V, N, res, 2.0)            # asserts a complex64 spectrum and a float32 grid inside
+    assert phi.dtype == np.float32 and phi.shape == res and phi[0, 0, 0] == 0.5
+    eref = np.abs(phi - sm.dpsr64(V, N, res, 2.0)).max()
+    print(f"dpsr32_cpu {res}: E_ref = {eref:.3e}")
+    assert measured / 3 < eref < measured * 3
+    assert eref < 2e-6                               # the ceiling test_phi_within_eref holds the recorded E_ref to
+
+
 def fields(n):
     x = np.linspace(-1, 1, n)
     X, Y, Z = np.meshgrid(x, x * 0.9, x * 1.1, indexing="ij")

@@ -5,25 +5,33 @@
 // Contract, in camera space (OpenCV axes):
 //   * every vertex is transformed once, x_c = ((R00 x + R01 y) + R02 z) + t0 (same for y_c, z_c), no FMA;
 //   * pixel (i, j) casts d = (((j + 0.5) - cx) / fx, ((i + 0.5) - cy) / fy, 1);
-//   * face (a, b, c): e_a = b x c, e_b = c x a, e_c = a x b, E_k = (e_k.x d.x + e_k.y d.y) + e_k.z; the ray covers the face
-//     when all E_k >= 0 or all E_k <= 0 and S = (E_a + E_b) + E_c != 0; lambda_k = E_k / S, z = (l_a z_a + l_b z_b) + l_c z_c;
-//     a hit counts when z_near < z < inf;
+//   * face (a, b, c): e_a = b x c, e_b = c x a, e_c = a x b, each component formed in fp64 from the fp32 vertices (exact
+//     products, one subtraction) and rounded to fp32 once; E_k = (e_k.x d.x + e_k.y d.y) + e_k.z in fp32; the ray covers
+//     the face when all E_k >= 0 or all E_k <= 0 and S = (E_a + E_b) + E_c != 0; lambda_k = E_k / S,
+//     z = (l_a z_a + l_b z_b) + l_c z_c; a hit counts when z_near < z < inf;
+//   * a face hits only pixels of its rectangle: the fp64 projected extent of the face clipped against z = z_near (1 - 2^-12),
+//     padded by one pixel, clamped to the image (face_setup; tests/mesh_raster_model.py pixel_rect).  The test is per
+//     pixel, so the image is a function of the ray and the face alone, never of where the 16 x 16 tile grid falls;
 //   * each pixel keeps the lexicographic minimum of (z, face id) over its hits.
-// Watertight by construction: the cross product u x v is computed as (u.y v.z - u.z v.y, ...), and with FMA contraction
-// off (Makefile: -ffp-contract=off) v x u is its exact negative (the products commute, round-to-nearest subtraction is
-// antisymmetric), and so is every E computed from it.  Two faces sharing the edge (b, c) therefore see exactly opposite
-// values of that edge's function on every ray: no ray passes between them, and a ray exactly on the edge (E = +-0) is
-// covered by both (the inclusive test), the lower id winning the z tie.
+// Watertight where the fp32 edge lines stay within the rectangle's one-pixel pad of the exact ones: the cross product
+// u x v is computed as (u.y v.z - u.z v.y, ...); the fp64 products commute, the fp64 subtraction is antisymmetric (FMA
+// contraction is off, Makefile: -ffp-contract=off) and rounding to fp32 is symmetric, so v x u is the exact negative of
+// u x v, and so is every E computed from it.  Two faces sharing the edge (b, c) therefore see exactly opposite values of
+// that edge's function on every ray: no ray passes between them, and a ray exactly on the edge (E = +-0) is covered by
+// both (the inclusive test), the lower id winning the z tie.  The rectangle can take such a hit away only where the
+// rounded edge function puts it more than a pixel outside the exact face: needles a few thousandths of a pixel wide,
+// thousands of pixels off the optical axis (INTEGRATION.md s15 gives the figures).
 //
 // MI355X design:
 //   * mesh_xform: one lane per vertex -> float4 camera-space positions.
 //   * face_setup: one lane per face: index check, edge functions (3 float4 per face), the culls (non-finite vertex,
-//     coincident vertices, wholly behind z_near, back face, off screen) and a conservative pixel rectangle from the face
-//     clipped against z = z_near in fp64, padded by one pixel.  The sort key is a lower bound of every z the face can
-//     produce (min z_k less 2^-16 relative, at least z_near).
+//     coincident vertices, wholly behind z_near, back face, off screen) and the pixel rectangle from the face clipped
+//     against z = z_near in fp64, padded by one pixel (two packed words per face; its tiles are what the face is binned
+//     to).  The sort key is a lower bound of every z the face can produce (min z_k less 2^-16 relative, at least z_near).
 //   * binning: per-face tile counts, an int64 exclusive scan, (tile << 32 | key bits, face) pairs emitted in face order,
 //     a stable LSD radix sort of the 64-bit keys (8-bit counting-sort passes) -> each tile's faces in (key, id) order.
-//   * mesh_walk: one 16 x 16 workgroup per tile; faces are staged 256 at a time in LDS.  A pixel stops once its best z is
+//   * mesh_walk: one 16 x 16 workgroup per tile; faces are staged 256 at a time in LDS (records, key, id, rectangle); a
+//     face counts for a pixel inside its rectangle that passes the sign test.  A pixel stops once its best z is
 //     below the next face's key (no later face can reach it); a wave stops when a ballot says all its pixels have; the
 //     workgroup stops loading batches when no pixel is left.  The result is a total-order minimum: independent of the
 //     processing order, bit-identical from run to run, no atomics on it.
@@ -74,6 +82,13 @@ __device__ __forceinline__ float3 cross3(float3 u, float3 v)
 {
 	return make_float3(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x);
 }
+// u x v with each component formed in fp64 (the products of two floats are exact there) and rounded to fp32 once: the
+// edge functions of thin faces seen far off-axis keep their direction, and edge3(v, u) is the exact negative of edge3(u, v)
+__device__ __forceinline__ float3 edge3(float3 u, float3 v)
+{
+	const double ux = u.x, uy = u.y, uz = u.z, vx = v.x, vy = v.y, vz = v.z;
+	return make_float3((float)(uy * vz - uz * vy), (float)(uz * vx - ux * vz), (float)(ux * vy - uy * vx));
+}
 __device__ __forceinline__ float3 sub3(float3 u, float3 v) { return make_float3(u.x - v.x, u.y - v.y, u.z - v.z); }
 __device__ __forceinline__ bool finite3(float3 u) { return isfinite(u.x) && isfinite(u.y) && isfinite(u.z); }
 __device__ __forceinline__ bool eq3(float3 u, float3 v) { return u.x == v.x && u.y == v.y && u.z == v.z; }
@@ -117,9 +132,11 @@ __device__ __forceinline__ void pixel_span(const Extent& e, int n, int& p0, int&
 }
 
 // rec[3f..3f+2] = {e_a.xyz, e_b.x}, {e_b.yz, e_c.xy}, {e_c.z, z_a, z_b, z_c}; rect[f] = tile rect (x0, y0, x1, y1), x0 > x1 = culled;
-// key[f] = the lower bound of the face's hit z; cnt[f] = tiles of the rect
+// prect[f] = the pixel rect (x0 | x1 << 16, y0 | y1 << 16), each bound below MAX_DIM; key[f] = the lower bound of the face's hit z;
+// cnt[f] = tiles of the rect
 __global__ void __launch_bounds__(256) face_setup(const float4* __restrict__ vc, int V, const int* __restrict__ faces, int F, Cam cam,
-                                                  float4* __restrict__ rec, int4* __restrict__ rect, float* __restrict__ key,
+                                                  float4* __restrict__ rec, int4* __restrict__ rect, uint2* __restrict__ prect,
+                                                  float* __restrict__ key,
                                                   long long* __restrict__ cnt, int* status)
 {
 	const int f = blockIdx.x * 256 + threadIdx.x;
@@ -171,9 +188,10 @@ __global__ void __launch_bounds__(256) face_setup(const float4* __restrict__ vc,
 	if (px0 > px1 || py0 > py1) return;
 	const int4 r = make_int4(px0 / TILE, py0 / TILE, px1 / TILE, py1 / TILE);
 	rect[f] = r;
+	prect[f] = make_uint2((unsigned)px0 | (unsigned)px1 << 16, (unsigned)py0 | (unsigned)py1 << 16);
 	cnt[f] = (long long)(r.z - r.x + 1) * (r.w - r.y + 1);
 	key[f] = kz;
-	const float3 ea = cross3(b, c), eb = cross3(c, a), ec = cross3(a, b);
+	const float3 ea = edge3(b, c), eb = edge3(c, a), ec = edge3(a, b);
 	rec[3 * (size_t)f] = make_float4(ea.x, ea.y, ea.z, eb.x);
 	rec[3 * (size_t)f + 1] = make_float4(eb.y, eb.z, ec.x, ec.y);
 	rec[3 * (size_t)f + 2] = make_float4(ec.z, a.z, b.z, c.z);
@@ -254,16 +272,19 @@ __global__ void __launch_bounds__(256) tile_ranges(const uint64_t* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------------ the walk
 __global__ void __launch_bounds__(256) mesh_walk(const int2* __restrict__ ranges, const uint64_t* __restrict__ keys,
-                                                 const int* __restrict__ vals, const float4* __restrict__ rec, Cam cam,
+                                                 const int* __restrict__ vals, const float4* __restrict__ rec,
+                                                 const uint2* __restrict__ prect, Cam cam,
                                                  int* __restrict__ pix_to_face, float* __restrict__ zbuf, float* __restrict__ bary)
 {
 	__shared__ float4 s_r0[256], s_r1[256], s_r2[256];
 	__shared__ float s_key[256];
 	__shared__ int s_id[256];
+	__shared__ uint2 s_pr[256];
 	const int tile = blockIdx.x;
 	const int tx = tile % cam.tiles_x, ty = tile / cam.tiles_x;
 	const int j = tx * TILE + (int)(threadIdx.x % TILE), i = ty * TILE + (int)(threadIdx.x / TILE);
 	const bool inside = i < cam.H && j < cam.W;
+	const unsigned uj = (unsigned)j, ui = (unsigned)i;
 	const float dx = (((float)j + 0.5f) - cam.cx) / cam.fx, dy = (((float)i + 0.5f) - cam.cy) / cam.fy;
 	float bz = INFINITY, la = -1.0f, lb = -1.0f, lc = -1.0f;
 	int bf = 0x7fffffff;
@@ -279,6 +300,7 @@ __global__ void __launch_bounds__(256) mesh_walk(const int2* __restrict__ ranges
 			s_r0[threadIdx.x] = rec[3 * (size_t)f];
 			s_r1[threadIdx.x] = rec[3 * (size_t)f + 1];
 			s_r2[threadIdx.x] = rec[3 * (size_t)f + 2];
+			s_pr[threadIdx.x] = prect[f];
 		}
 		__syncthreads();
 		for (int k = 0; k < n; k++) {
@@ -291,7 +313,9 @@ __global__ void __launch_bounds__(256) mesh_walk(const int2* __restrict__ ranges
 			const float Ec = (r1.z * dx + r1.w * dy) + r2.x;
 			const bool pos = Ea >= 0.0f && Eb >= 0.0f && Ec >= 0.0f, neg = Ea <= 0.0f && Eb <= 0.0f && Ec <= 0.0f;
 			const float S = (Ea + Eb) + Ec;
-			if (!(pos || neg) || S == 0.0f) continue;
+			const uint2 pr = s_pr[k];   // the face's pixel rectangle: outside it the face hits nothing
+			const bool in = uj >= (pr.x & 0xffffu) && uj <= (pr.x >> 16) && ui >= (pr.y & 0xffffu) && ui <= (pr.y >> 16);
+			if (!(pos || neg) || S == 0.0f || !in) continue;
 			const float pa = Ea / S, pb = Eb / S, pc = Ec / S;
 			const float z = (pa * r2.y + pb * r2.z) + pc * r2.w;
 			const int f = s_id[k];
@@ -432,13 +456,14 @@ int gsr_mesh_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const 
 
 	// pass 1: per vertex / per face setup and the tile counts
 	Sizer z1;
-	z1.add<float4>(V); z1.add<float4>(3 * (size_t)F); z1.add<int4>(F); z1.add<float>(F); z1.add<long long>(F);
+	z1.add<float4>(V); z1.add<float4>(3 * (size_t)F); z1.add<int4>(F); z1.add<uint2>(F); z1.add<float>(F); z1.add<long long>(F);
 	z1.add<long long>((size_t)F + 1); z1.add<long long>(scan_part_len(F)); z1.add<int>(1); z1.add<int2>(T);
 	Arena w1{ws_alloc(workspace_alloc, workspace_ctx, z1.bytes), 0};
 	if (!w1.p) return GSR_ERR_ALLOC;
 	float4* vc = w1.take<float4>(V);
 	float4* rec = w1.take<float4>(3 * (size_t)F);
 	int4* rect = w1.take<int4>(F);
+	uint2* prect = w1.take<uint2>(F);
 	float* key = w1.take<float>(F);
 	long long* cnt = w1.take<long long>(F);
 	long long* off = w1.take<long long>((size_t)F + 1);
@@ -451,7 +476,7 @@ int gsr_mesh_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const 
 	int st = 0;
 	if (F > 0) {
 		if (V > 0) hipLaunchKernelGGL(mesh_xform, dim3(blocks(V)), dim3(256), 0, s, verts, V, cam, vc);
-		hipLaunchKernelGGL(face_setup, dim3(blocks(F)), dim3(256), 0, s, vc, V, faces, F, cam, rec, rect, key, cnt, status);
+		hipLaunchKernelGGL(face_setup, dim3(blocks(F)), dim3(256), 0, s, vc, V, faces, F, cam, rec, rect, prect, key, cnt, status);
 		const int rc = exclusive_scan<long long>(cnt, F, off, part, s);
 		if (rc) return rc;
 		MR_TRY(hipMemcpyAsync(&R, off + F, sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -478,7 +503,7 @@ int gsr_mesh_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const 
 		if (rc) return rc;
 		hipLaunchKernelGGL(tile_ranges, dim3(blocks(n)), dim3(256), 0, s, k0, n, ranges);
 	}
-	hipLaunchKernelGGL(mesh_walk, dim3(T), dim3(256), 0, s, ranges, k0, v0, rec, cam, pix_to_face, zbuf, bary);
+	hipLaunchKernelGGL(mesh_walk, dim3(T), dim3(256), 0, s, ranges, k0, v0, rec, prect, cam, pix_to_face, zbuf, bary);
 	MR_TRY(hipGetLastError());
 	return n;
 }

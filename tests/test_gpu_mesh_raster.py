@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mesh_raster_model as mm  # noqa: E402
+from mesh_raster_model import random_scene, sphere_grid  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -37,16 +38,6 @@ def assert_bit_equal(got, want, what=""):
         assert a.shape == b.shape, f"{what} {n} shape"
         same = a.view(np.int32) == b.view(np.int32)
         assert same.all(), f"{what} {n}: {np.count_nonzero(~same)} values differ from the float32 replay"
-
-
-def random_scene(rng, F, crossing=False):
-    V = 2 * F
-    if crossing:   # a cloud around the camera: many faces cross the camera plane
-        v = rng.uniform(-2, 2, size=(V, 3)) + [0, 0, 0.8]
-    else:
-        v = rng.uniform(-1, 1, size=(V, 3)) * [1.2, 1.0, 0.7] + [0, 0, 3]
-    f = rng.integers(0, V, size=(F, 3))
-    return v.astype(np.float32), f.astype(np.int32)
 
 
 @pytest.mark.parametrize("case", range(8))
@@ -236,22 +227,6 @@ def test_negative_zero_camera_z_keeps_its_place_in_the_tile_order():
     _, _, got = gpu(v, f, k, E, 32, 32)
     assert_bit_equal(got, mm.rasterize(v, f, k, E, 32, 32), "-0 key")
     assert (got[0] == 2).sum() > 20
-
-
-def sphere_grid(nu, nv, seed=0):
-    """A bumpy closed-ish sphere from an nu x nv lat-long grid: 2 nu nv faces."""
-    rng = np.random.default_rng(seed)
-    th = (np.arange(nv + 1) + 0.5) / (nv + 1) * np.pi
-    ph = np.arange(nu) / nu * 2 * np.pi
-    T, P = np.meshgrid(th, ph, indexing="ij")
-    r = 1 + 0.05 * np.sin(7 * P) * np.sin(5 * T) + 0.002 * rng.random(T.shape)
-    v = np.stack([r * np.sin(T) * np.cos(P), r * np.cos(T), r * np.sin(T) * np.sin(P)], -1).reshape(-1, 3)
-    iv, iu = np.meshgrid(np.arange(nv), np.arange(nu), indexing="ij")
-    a = iv * nu + iu
-    b = iv * nu + (iu + 1) % nu
-    c, d = a + nu, b + nu
-    f = np.concatenate([np.stack([a, c, b], -1).reshape(-1, 3), np.stack([b, c, d], -1).reshape(-1, 3)])
-    return v.astype(np.float32), f.astype(np.int32)
 
 
 def test_large_mesh_1080p_against_float64_model():

@@ -7,7 +7,8 @@ each for rasterize (the whole call: setup, binning with its one host read, sort,
 normal_map, visible_faces and vertex_normals.
 
     python tools/mesh_raster_timing.py [--repeat 10]
-Prints one line per measurement (median of --repeat runs after one warm-up) and a JSON summary line.
+Prints one line per measurement (median of --repeat runs after one warm-up) and a JSON summary line; the summary also
+holds each measurement's least and greatest repeat ("<name>_range"), the run-to-run spread to judge a difference by.
 """
 import argparse
 import json
@@ -67,7 +68,7 @@ def gpu_time(fn, repeat):
         fn()
         torch.cuda.synchronize()
         ts.append(time.perf_counter() - t0)
-    return statistics.median(ts) * 1e3
+    return statistics.median(ts) * 1e3, [min(ts) * 1e3, max(ts) * 1e3]
 
 
 def tsdf_mesh():
@@ -102,18 +103,22 @@ def measure(name, verts, faces, K, E, H, W, repeat):
     res["covered_pixels"] = int((fr.pix_to_face >= 0).sum())
     res["binned_entries"] = int(r.last_binned)
     attr = torch.rand((verts.shape[0], 3), device=DEV)
-    res["rasterize_ms"] = gpu_time(lambda: r.rasterize(K, E, H, W), repeat)
-    res["rasterize_cull_ms"] = gpu_time(lambda: r.rasterize(K, E, H, W, cull_backfaces=True), repeat)
-    res["interpolate3_ms"] = gpu_time(lambda: r.interpolate(fr, attr), repeat)
+
+    def timed(key, fn):
+        res[key], res[key + "_range"] = gpu_time(fn, repeat)
+    timed("rasterize_ms", lambda: r.rasterize(K, E, H, W))
+    timed("rasterize_cull_ms", lambda: r.rasterize(K, E, H, W, cull_backfaces=True))
+    timed("interpolate3_ms", lambda: r.interpolate(fr, attr))
     r.vertex_normals()
-    res["normal_map_ms"] = gpu_time(lambda: r.normal_map(fr, E), repeat)
-    res["visible_faces_ms"] = gpu_time(lambda: r.visible_faces(fr), repeat)
+    timed("normal_map_ms", lambda: r.normal_map(fr, E))
+    timed("visible_faces_ms", lambda: r.visible_faces(fr))
 
     def vn():
         r._normals = None
         r.vertex_normals()
-    res["vertex_normals_ms"] = gpu_time(vn, repeat)
-    print(name, " ".join(f"{k}={v:.3f}" if isinstance(v, float) else f"{k}={v}" for k, v in res.items()), flush=True)
+    timed("vertex_normals_ms", vn)
+    print(name, " ".join(f"{k}={v:.3f}" if isinstance(v, float) else f"{k}={v}" for k, v in res.items() if not k.endswith("_range")),
+          flush=True)
     return res
 
 

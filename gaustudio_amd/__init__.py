@@ -10,5 +10,7 @@ from .options import options  # noqa: F401,E402  (per-call options: tile band, f
 from .tsdf_rgbd import ColorTSDFVolume, fuse_rgbd  # noqa: F401,E402  (coloured TSDF fusion of posed RGB-D frames)
 from .visual_hull import VisualHull, carve, visual_hull_init  # noqa: F401,E402  (silhouette carving and Gaussian seeds)
 from .voxelize import VoxelGrid, closest_on_mesh, voxel_init, voxel_seeds, voxelize_mesh  # noqa: F401,E402  (mesh -> voxels -> Gaussian seeds)
+# point cloud -> Gaussian seeds; `gaustudio_amd.pcd_init` stays the module (its function of that name is pcd_init.pcd_init)
+from .pcd_init import depth_seeds, mean_dist2, pcd_init_from_ply, point_seeds, sky_seeds  # noqa: F401,E402
 
 __version__ = "0.1.0"

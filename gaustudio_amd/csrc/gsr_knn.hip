@@ -16,6 +16,8 @@
 //     so each id's records are reduced in record order (view order, then pixel order), one lane per id, in fp64: no
 //     float atomics, bit-identical output from run to run.
 //   * Cleaning: fixed-shape fp64 block reductions for the mean and the standard deviation of the mean kNN distance.
+//   * 3-NN mean distance (simple-knn's distCUDA2): the same grid at ~4 points per cell, one LANE per point in
+//     cell order, three fp64 distances in registers, shells 0..2; what is not settled then goes through the wave-per-query kNN.
 // All memory is caller-owned or obtained through the gsr_alloc_fn callback; the entry points are stateless.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -32,6 +34,7 @@ constexpr int CELL_BITS = 21;
 constexpr int CELL_MAX = (1 << CELL_BITS) - 1;
 constexpr int SHELL_MAX = 2;            // shells scanned around the query cell before the full cell scan
 constexpr int NO_INDEX = 0x7fffffff;
+constexpr int DIST3_CELL_TARGET = 4;    // points per occupied cell for dist3_query (DESIGN.md s19 has the measurements)
 
 struct Grid {
 	double ox, oy, oz;   // origin (bounding-box minimum)
@@ -286,6 +289,96 @@ __global__ void __launch_bounds__(256) knn_query(Grid g, const unsigned long lon
 	}
 }
 
+// ------------------------------------------------------------------------------------------------------ 3-NN mean distance
+// simple-knn's distCUDA2 / calculate_dist2_python (gaustudio/models/vanilla_sg.py:9-14): the mean of the squared distances to
+// the three nearest OTHER points.  One lane per sorted position of spts, so the 64 lanes of a wave lie in the same few cells
+// and walk nearly the same cell lists (their loads hit the same lines).  Only the three smallest VALUES are kept (six VGPRs,
+// a min / max insertion network, no index): ties need no order, and the order the atomics gave the points inside a cell
+// does not reach the result.  No LDS; every loop is bounded by a cell count or the table mask.
+struct Best3 {
+	double d1, d2, d3;   // ascending; +inf = empty
+};
+__device__ __forceinline__ void insert3(Best3& b, double d)
+{
+	const double t = fmax(b.d1, d);
+	b.d1 = fmin(b.d1, d);
+	const double u = fmax(b.d2, t);
+	b.d2 = fmin(b.d2, t);
+	b.d3 = fmin(b.d3, u);
+}
+
+// the cells at Chebyshev distance R of (cx, cy, cz)
+template <int R>
+__device__ __forceinline__ void scan_shell3(Best3& b, const Grid& g, const unsigned long long* __restrict__ keys,
+                                            const int* __restrict__ start, const int* __restrict__ cnt,
+                                            const float4* __restrict__ spts, int cx, int cy, int cz, double qx, double qy, double qz,
+                                            int self)
+{
+	constexpr int side = 2 * R + 1, ncube = side * side * side;
+#pragma unroll 1
+	for (int e = 0; e < ncube; e++) {
+		const int ox = e % side - R, oy = (e / side) % side - R, oz = e / (side * side) - R;
+		if (max(abs(ox), max(abs(oy), abs(oz))) != R) continue;
+		const int x = cx + ox, y = cy + oy, z = cz + oz;
+		if (x < 0 || y < 0 || z < 0 || x > CELL_MAX || y > CELL_MAX || z > CELL_MAX) continue;
+		const int s = find_slot(keys, g.mask, cell_key(x, y, z));
+		if (s < 0) continue;
+		const int c0 = start[s], c1 = c0 + cnt[s];
+		for (int j = c0; j < c1; j++) {
+			const float4 p = spts[j];
+			if (__float_as_int(p.w) == self) continue;
+			const double dx = (double)p.x - qx, dy = (double)p.y - qy, dz = (double)p.z - qz;
+			insert3(b, dx * dx + dy * dy + dz * dz);
+		}
+	}
+}
+
+// knn_query's settle test: every unseen point lies outside the cube of shells 0..r, at least `bound` away
+__device__ __forceinline__ bool settled3(const Best3& b, const Grid& g, int cx, int cy, int cz, int r, double qx, double qy, double qz)
+{
+	if (b.d3 == HUGE_VAL) return false;
+	const double lx = qx - (g.ox + (cx - r) * g.h), hx = g.ox + (cx + r + 1) * g.h - qx;
+	const double ly = qy - (g.oy + (cy - r) * g.h), hy = g.oy + (cy + r + 1) * g.h - qy;
+	const double lz = qz - (g.oz + (cz - r) * g.h), hz = g.oz + (cz + r + 1) * g.h - qz;
+	const double bound = fmin(fmin(fmin(lx, hx), fmin(ly, hy)), fmin(lz, hz)) - g.margin;
+	return bound > 0.0 && b.d3 < bound * bound;
+}
+
+// stat[0] = lanes that needed shell 2, stat[1] = lanes left unsettled: their original indices go to leftover[] (any order)
+__global__ void __launch_bounds__(256) dist3_query(Grid g, const unsigned long long* __restrict__ keys, const int* __restrict__ start,
+                                                   const int* __restrict__ cnt, const float4* __restrict__ spts, int n,
+                                                   float* __restrict__ out, int* __restrict__ leftover, int* stat)
+{
+	const int pos = blockIdx.x * 256 + threadIdx.x;
+	if (pos >= n) return;
+	const float4 q = spts[pos];
+	const int self = __float_as_int(q.w);
+	const double qx = q.x, qy = q.y, qz = q.z;
+	const int cx = cell_of(q.x, g.ox, g.inv_h), cy = cell_of(q.y, g.oy, g.inv_h), cz = cell_of(q.z, g.oz, g.inv_h);
+	Best3 b{HUGE_VAL, HUGE_VAL, HUGE_VAL};
+	scan_shell3<0>(b, g, keys, start, cnt, spts, cx, cy, cz, qx, qy, qz, self);
+	scan_shell3<1>(b, g, keys, start, cnt, spts, cx, cy, cz, qx, qy, qz, self);
+	bool done = settled3(b, g, cx, cy, cz, 1, qx, qy, qz);
+	const uint64_t m = __ballot(!done);   // one atomic per wave for the count
+	if (!done && (int)(threadIdx.x & 63) == __ffsll((unsigned long long)m) - 1) atomicAdd(&stat[0], __popcll(m));
+	if (!done) {
+		scan_shell3<2>(b, g, keys, start, cnt, spts, cx, cy, cz, qx, qy, qz, self);
+		done = settled3(b, g, cx, cy, cz, 2, qx, qy, qz);
+	}
+	if (done) out[self] = (float)(((b.d1 + b.d2) + b.d3) / 3.0);
+	else leftover[atomicAdd(&stat[1], 1)] = self;
+}
+
+// the leftovers' kNN rows (k = 4, entry 0 is the point itself or a duplicate of it: distance 0, the minimum) into out
+__global__ void __launch_bounds__(256) dist3_fold(const double* __restrict__ d2, const int* __restrict__ leftover, int m,
+                                                  float* __restrict__ out)
+{
+	const int j = blockIdx.x * 256 + threadIdx.x;
+	if (j >= m) return;
+	const double* d = d2 + 4 * (size_t)j;
+	out[leftover[j]] = (float)(((d[1] + d[2]) + d[3]) / 3.0);
+}
+
 // ------------------------------------------------------------------------------------------------------ host helpers
 struct Arena {   // bump allocation out of one workspace block
 	char* p;
@@ -318,9 +411,18 @@ size_t knn_bytes(int n, int nq, int k, bool want_out)
 
 #define KN_TRY(expr) do { if ((expr) != hipSuccess) return GSR_ERR_HIP; } while (0)
 
-// builds the grid over `pts` in `ws` and answers the queries; ws must hold knn_bytes(n, .., false)
-int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, int k, double* dist2, int64_t* idx,
-            hipStream_t s)
+// the hashed grid over `pts`, carved out of `ws` (knn_bytes(n, .., false)) by grid_build
+struct GridBufs {
+	Grid g;
+	unsigned long long* keys;
+	int *cnt, *start, *cells;
+	float4* spts;
+	int* counters;   // [0..2] the build's, [3] a query that is not finite, [4..6] dist3_query's, [8..14] the bounding box
+	int occupied, ncells;
+};
+
+// builds the grid with ~m_target points per occupied cell (and no more than CELL_MAX cells along an axis)
+int grid_build(Arena& ws, const float* pts, int n, double m_target, GridBufs& gb, hipStream_t s)
 {
 	const uint64_t T = table_size(n);
 	unsigned long long* keys = ws.take<unsigned long long>(T);
@@ -346,11 +448,10 @@ int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, in
 		lo[a] = unordered(bbox[a]);
 		ext = fmax(ext, (double)unordered(bbox[3 + a]) - lo[a]);
 	}
-	// cell size: ~m_target points per occupied cell, and no more than CELL_MAX cells along an axis
-	const double m_target = fmin(fmax(k * 0.5, 8.0), 32.0);
 	const double h_min = ext / (CELL_MAX - 1);
 	double h = ext > 0.0 ? fmax(ext / cbrt(fmax((double)n / m_target, 1.0)), h_min) : 1.0;
 	Grid g{lo[0], lo[1], lo[2], h, 1.0 / h, 1e-6 * h, T - 1};
+	int occupied = 0;
 	for (int it = 0;; it++) {
 		g.h = h; g.inv_h = 1.0 / h; g.margin = 1e-6 * h;
 		KN_TRY(hipMemsetAsync(keys, 0xff, T * 8, s));
@@ -358,7 +459,6 @@ int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, in
 		KN_TRY(hipMemsetAsync(counters, 0, 8 * sizeof(int), s));
 		hipLaunchKernelGGL(grid_insert, dim3(nb), dim3(256), 0, s, pts, n, g, keys, pslot, cnt, counters);
 		KN_TRY(hipGetLastError());
-		int occupied = 0;
 		KN_TRY(hipMemcpyAsync(&occupied, counters, sizeof(int), hipMemcpyDeviceToHost, s));
 		KN_TRY(hipStreamSynchronize(s));
 		const double ratio = m_target / ((double)n / (double)(occupied > 0 ? occupied : 1));
@@ -371,17 +471,34 @@ int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, in
 	int ncells = 0;
 	KN_TRY(hipMemcpyAsync(&ncells, counters + 2, sizeof(int), hipMemcpyDeviceToHost, s));
 	KN_TRY(hipStreamSynchronize(s));
+	gb = GridBufs{g, keys, cnt, start, cells, spts, counters, occupied, ncells};
+	return GSR_OK;
+}
+
+// answers the queries from a built grid, one wave per query
+int knn_answer(const GridBufs& gb, const float* queries, int nq, int k, double* dist2, int64_t* idx, bool check_queries, hipStream_t s)
+{
 	if (nq > 0)   // counters[3] (zeroed with the grid's counters): set by a query that is not finite
-		hipLaunchKernelGGL(knn_query, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, g, keys, start, cnt, cells, ncells, spts,
-		                   queries, nq, k, dist2, idx, counters + 3);
+		hipLaunchKernelGGL(knn_query, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, gb.g, gb.keys, gb.start, gb.cnt, gb.cells, gb.ncells,
+		                   gb.spts, queries, nq, k, dist2, idx, gb.counters + 3);
 	KN_TRY(hipGetLastError());
-	if (nq > 0 && queries != pts) {   // the points themselves were checked with the bounding box
+	if (nq > 0 && check_queries) {
 		int qbad = 0;
-		KN_TRY(hipMemcpyAsync(&qbad, counters + 3, sizeof(int), hipMemcpyDeviceToHost, s));
+		KN_TRY(hipMemcpyAsync(&qbad, gb.counters + 3, sizeof(int), hipMemcpyDeviceToHost, s));
 		KN_TRY(hipStreamSynchronize(s));
 		if (qbad) return GSR_ERR_NONFINITE_QUERY;
 	}
 	return GSR_OK;
+}
+
+// builds the grid over `pts` in `ws` and answers the queries; ws must hold knn_bytes(n, .., false)
+int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, int k, double* dist2, int64_t* idx,
+            hipStream_t s)
+{
+	GridBufs gb;
+	const int rc = grid_build(ws, pts, n, fmin(fmax(k * 0.5, 8.0), 32.0), gb, s);   // ~k/2 points per occupied cell
+	if (rc) return rc;
+	return knn_answer(gb, queries, nq, k, dist2, idx, queries != pts, s);   // the points themselves were checked with the bounding box
 }
 
 char* ws_alloc(gsr_alloc_fn alloc, void* ctx, size_t bytes)
@@ -604,6 +721,65 @@ int gsr_knn(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* poin
 	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, knn_bytes(num_points, 0, k, false)), 0};
 	if (!ws.p) return GSR_ERR_ALLOC;
 	return knn_run(ws, points, num_points, queries, num_queries, k, dist2, indices, (hipStream_t)stream);
+}
+
+int gsr_mean_dist3_ex(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, float* out_dist2,
+                      int cell_target, int stats[3], float stage_ms[3], void* stream)
+{
+	if (!points || num_points < 4 || !out_dist2 || cell_target < 0 || cell_target > 64) return GSR_ERR_ARG;
+	hipStream_t s = (hipStream_t)stream;
+	const int n = num_points;
+	const size_t left_bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
+	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, knn_bytes(n, 0, 4, false) + left_bytes), 0};
+	if (!ws.p) return GSR_ERR_ALLOC;
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	if (stage_ms)
+		for (int j = 0; j < 4; j++) KN_TRY(hipEventCreate(&ev[j]));
+	struct EventGuard {
+		hipEvent_t* e;
+		~EventGuard() { for (int j = 0; j < 4; j++) if (e[j]) (void)hipEventDestroy(e[j]); }
+	} guard{ev};
+	if (stage_ms) KN_TRY(hipEventRecord(ev[0], s));
+	GridBufs gb;
+	int rc = grid_build(ws, points, n, cell_target ? (double)cell_target : (double)DIST3_CELL_TARGET, gb, s);
+	if (rc) return rc;
+	int* leftover = ws.take<int>(n);
+	int* stat = gb.counters + 4;   // zeroed with the grid's counters
+	if (stage_ms) KN_TRY(hipEventRecord(ev[1], s));
+	hipLaunchKernelGGL(dist3_query, dim3(blocks(n)), dim3(256), 0, s, gb.g, gb.keys, gb.start, gb.cnt, gb.spts, n, out_dist2, leftover, stat);
+	KN_TRY(hipGetLastError());
+	if (stage_ms) KN_TRY(hipEventRecord(ev[2], s));
+	int st[2] = {0, 0};
+	KN_TRY(hipMemcpyAsync(st, stat, sizeof(st), hipMemcpyDeviceToHost, s));
+	KN_TRY(hipStreamSynchronize(s));
+	const int m = st[1];
+	if (m < 0 || m > n) return GSR_ERR_HIP;
+	if (m > 0) {   // far outliers, sparse regions, n close to 4: the wave-per-query search, which scans every occupied cell
+		auto r = [](size_t x) { return (x + 255) & ~(size_t)255; };
+		Arena w2{ws_alloc(workspace_alloc, workspace_ctx, r((size_t)m * 12) + 2 * r((size_t)m * 32)), 0};
+		if (!w2.p) return GSR_ERR_ALLOC;
+		float* q = w2.take<float>((size_t)m * 3);
+		double* d2 = w2.take<double>((size_t)m * 4);
+		int64_t* nbr = w2.take<int64_t>((size_t)m * 4);
+		hipLaunchKernelGGL(gather_points, dim3(blocks(m)), dim3(256), 0, s, points, leftover, m, q);
+		rc = knn_answer(gb, q, m, 4, d2, nbr, false, s);
+		if (rc) return rc;
+		hipLaunchKernelGGL(dist3_fold, dim3(blocks(m)), dim3(256), 0, s, d2, leftover, m, out_dist2);
+		KN_TRY(hipGetLastError());
+	}
+	if (stage_ms) {
+		KN_TRY(hipEventRecord(ev[3], s));
+		KN_TRY(hipEventSynchronize(ev[3]));
+		for (int j = 0; j < 3; j++) KN_TRY(hipEventElapsedTime(&stage_ms[j], ev[j], ev[j + 1]));
+	}
+	if (stats) { stats[0] = gb.occupied; stats[1] = st[0]; stats[2] = m; }
+	return GSR_OK;
+}
+
+int gsr_mean_dist3(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, float* out_dist2,
+                   int stats[3], void* stream)
+{
+	return gsr_mean_dist3_ex(workspace_alloc, workspace_ctx, points, num_points, out_dist2, 0, stats, nullptr, stream);
 }
 
 int gsr_fusion_records(const float* xyz, int num_gaussians, const int* ids, const float* normals, const float* confidences,

@@ -171,6 +171,26 @@ __device__ __forceinline__ float3 bary3(const float* b, float3 a0, float3 a1, fl
 	                   (b[0] * a0.z + b[1] * a1.z) + b[2] * a2.z);
 }
 
+// normal2rotation after its F.normalize (n is the normalised normal) and rotmat2quaternion, not normalised: q[4] = (w, x, y, z)
+__device__ __forceinline__ void normal_quat(float3 n, float* __restrict__ q)
+{
+	const float dot = (1.0f * n.x + 0.0f * n.y) + 0.0f * n.z;
+	float3 r0 = make_float3(1.0f - dot * n.x, 0.0f - dot * n.y, 0.0f - dot * n.z);
+	const float s0 = sign1(r0.x);
+	r0 = normalize3(make_float3(r0.x * s0, r0.y * s0, r0.z * s0));
+	float3 r1 = cross3f(n, r0);
+	const float s1 = sign1(r1.y) * sign1(n.z);
+	r1 = make_float3(r1.x * s1, r1.y * s1, r1.z * s1);
+	// R = [r0 | r1 | n] (columns)
+	const float tr = ((r0.x + r1.y) + n.z) + 1e-6f;
+	const float q0 = sqrtf(1.0f + tr) / 2.0f;
+	const float q4 = 4.0f * q0;
+	q[0] = q0;
+	q[1] = (r1.z - n.y) / q4;
+	q[2] = (n.x - r0.z) / q4;
+	q[3] = (r0.y - r1.x) / q4;
+}
+
 __global__ void __launch_bounds__(256) mesh_seeds(const float* __restrict__ verts, const float* __restrict__ normals,
                                                   const float* __restrict__ vcolors, int V, const int* __restrict__ faces,
                                                   long long P, SeedTable tb, float* __restrict__ xyz, float* __restrict__ f_dc,
@@ -201,22 +221,60 @@ __global__ void __launch_bounds__(256) mesh_seeds(const float* __restrict__ vert
 	store3(scale, (size_t)g, make_float3(ls, ls, tb.log_eps));
 
 	// _compute_surface_normals (one F.normalize) -> normal2rotation (a second one)
-	const float3 n = normalize3(normalize3(bary3(b, load3(normals, i0), load3(normals, i1), load3(normals, i2))));
-	const float dot = (1.0f * n.x + 0.0f * n.y) + 0.0f * n.z;
-	float3 r0 = make_float3(1.0f - dot * n.x, 0.0f - dot * n.y, 0.0f - dot * n.z);
-	const float s0 = sign1(r0.x);
-	r0 = normalize3(make_float3(r0.x * s0, r0.y * s0, r0.z * s0));
-	float3 r1 = cross3f(n, r0);
-	const float s1 = sign1(r1.y) * sign1(n.z);
-	r1 = make_float3(r1.x * s1, r1.y * s1, r1.z * s1);
-	// R = [r0 | r1 | n] (columns); rotmat2quaternion, not normalised
-	const float tr = ((r0.x + r1.y) + n.z) + 1e-6f;
-	const float q0 = sqrtf(1.0f + tr) / 2.0f;
-	const float q4 = 4.0f * q0;
-	rot[4 * (size_t)g] = q0;
-	rot[4 * (size_t)g + 1] = (r1.z - n.y) / q4;
-	rot[4 * (size_t)g + 2] = (n.x - r0.z) / q4;
-	rot[4 * (size_t)g + 3] = (r0.y - r1.x) / q4;
+	normal_quat(normalize3(normalize3(bary3(b, load3(normals, i0), load3(normals, i1), load3(normals, i2)))), rot + 4 * (size_t)g);
+}
+
+// ------------------------------------------------------------------------------------------------------ point seeds
+// VanillaPointCloud.create_from_attribute (gaustudio/models/vanilla_sg.py:69-97), one lane per point.  An absent input is
+// NULL: rgb -> 1; scale_in -> log(sqrt(dist2 + 1e-7)) on all three axes; rot_in -> normal2rotation(normals), or (1, 0, 0, 0)
+// without normals; opacity_in -> the scalar.
+__global__ void __launch_bounds__(256) point_seeds(const float* __restrict__ xyz, const float* __restrict__ rgb,
+                                                   const float* __restrict__ dist2, const float* __restrict__ scale_in,
+                                                   const float* __restrict__ rot_in, const float* __restrict__ normals,
+                                                   const float* __restrict__ opacity_in, float opacity, float c0, int n,
+                                                   float* __restrict__ xyz_out, float* __restrict__ f_dc, float* __restrict__ scale,
+                                                   float* __restrict__ rot, float* __restrict__ opacity_out)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	store3(xyz_out, (size_t)i, load3(xyz, i));
+	const float3 c = rgb ? load3(rgb, i) : make_float3(1.0f, 1.0f, 1.0f);
+	store3(f_dc, (size_t)i, make_float3((c.x - 0.5f) / c0, (c.y - 0.5f) / c0, (c.z - 0.5f) / c0));
+	if (scale_in) {
+		store3(scale, (size_t)i, load3(scale_in, i));
+	} else {
+		const float ls = (float)log((double)sqrtf(dist2[i] + 1e-7f));
+		store3(scale, (size_t)i, make_float3(ls, ls, ls));
+	}
+	float* q = rot + 4 * (size_t)i;
+	if (rot_in) {
+		for (int a = 0; a < 4; a++) q[a] = rot_in[4 * (size_t)i + a];
+	} else if (normals) {
+		normal_quat(normalize3(load3(normals, i)), q);
+	} else {
+		q[0] = 1.0f; q[1] = 0.0f; q[2] = 0.0f; q[3] = 0.0f;
+	}
+	opacity_out[i] = opacity_in ? opacity_in[i] : opacity;
+}
+
+// DepthInitializer's float16 cache file and uint8 colours (gaustudio/pipelines/initializers/depth.py:50-89) without the disk:
+// one lane per pixel of one frame
+__device__ __forceinline__ float half_round(float x) { return (float)(_Float16)x; }
+__global__ void __launch_bounds__(256) depth_seed_pack(const float* __restrict__ points, const float* __restrict__ image,
+                                                       const float* __restrict__ depth, int n, float focal,
+                                                       float* __restrict__ xyz, float* __restrict__ rgb, float* __restrict__ scale)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const float3 p = load3(points, i), c = load3(image, i);
+	store3(xyz, (size_t)i, make_float3(half_round(p.x), half_round(p.y), half_round(p.z)));
+	float col[3] = {c.x, c.y, c.z};
+	for (int a = 0; a < 3; a++)   // half(c) * 255 in half, truncated to uint8, / 255 in float32
+		col[a] = (float)(unsigned char)(int)half_round(half_round(col[a]) * 255.0f) / 255.0f;
+	store3(rgb, (size_t)i, make_float3(col[0], col[1], col[2]));
+	const float s = half_round(depth[i] / focal);
+	const float ls = half_round((float)log((double)s));   // numpy's float16 log: through float32
+	store3(scale, (size_t)i, make_float3(ls, ls, ls));
 }
 
 #define MB_TRY(expr) do { if ((expr) != hipSuccess) return GSR_ERR_HIP; } while (0)
@@ -321,6 +379,31 @@ int gsr_mesh_seeds(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const floa
 	MB_TRY(hipMemcpyAsync(&st, status, sizeof(int), hipMemcpyDeviceToHost, s));
 	MB_TRY(hipStreamSynchronize(s));
 	return st ? GSR_ERR_ARG : GSR_OK;
+}
+
+int gsr_point_seeds(const float* xyz, const float* rgb, const float* dist2, const float* scale_in, const float* rot_in,
+                    const float* normals, const float* opacity_in, float opacity, int num_points, float* xyz_out, float* f_dc,
+                    float* scale, float* rot, float* opacity_out, void* stream)
+{
+	if (num_points < 0 || (rot_in && normals)) return GSR_ERR_ARG;
+	if (num_points == 0) return GSR_OK;
+	if (!xyz || (!dist2 == !scale_in) || !xyz_out || !f_dc || !scale || !rot || !opacity_out) return GSR_ERR_ARG;
+	hipLaunchKernelGGL(point_seeds, dim3(blocks(num_points)), dim3(256), 0, (hipStream_t)stream, xyz, rgb, dist2, scale_in, rot_in,
+	                   normals, opacity_in, opacity, (float)0.28209479177387814, num_points, xyz_out, f_dc, scale, rot, opacity_out);
+	MB_TRY(hipGetLastError());
+	return GSR_OK;
+}
+
+int gsr_depth_seed_pack(const float* points, const float* image, const float* depth, int num_pixels, float focal, float* xyz,
+                        float* rgb, float* scale, void* stream)
+{
+	if (num_pixels < 0) return GSR_ERR_ARG;
+	if (num_pixels == 0) return GSR_OK;
+	if (!points || !image || !depth || !xyz || !rgb || !scale) return GSR_ERR_ARG;
+	hipLaunchKernelGGL(depth_seed_pack, dim3(blocks(num_pixels)), dim3(256), 0, (hipStream_t)stream, points, image, depth, num_pixels,
+	                   focal, xyz, rgb, scale);
+	MB_TRY(hipGetLastError());
+	return GSR_OK;
 }
 
 }  // extern "C"

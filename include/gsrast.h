@@ -827,6 +827,41 @@ int gsr_mesh_seeds(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const floa
                    const float* vertex_colors, int num_verts, const int* faces, int num_faces, int n_per_triangle, float* xyz,
                    float* f_dc, float* scale, float* rot, void* stream);
 
+/* ---- Gaussian seeds from a point cloud: what every point-cloud initializer of the reference ends in
+ * (VanillaPointCloud.create_from_attribute, gaustudio/models/vanilla_sg.py:69-97, with simple-knn's distCUDA2 /
+ * calculate_dist2_python for scale=None), and DepthInitializer's float16 packing.  Additive to ABI 6, in the style of gsr_knn /
+ * gsr_mesh_seeds.  Contract: INTEGRATION.md s22; design: gsr_knn.hip, gsr_mesh_bake.hip, DESIGN.md s19. ---- */
+
+/* out_dist2[i] (f32) = (float)(((d1 + d2) + d3) / 3.0) with d1 <= d2 <= d3 the three smallest squared distances from point i to
+ * the OTHER points (another index; a duplicate coordinate counts, at 0), each dx*dx + dy*dy + dz*dz in f64 from the f32
+ * coordinates, summed in that order.  Only values enter: fully determined, bit-identical from run to run.  4 <= num_points
+ * (GSR_ERR_ARG otherwise); GSR_ERR_NONFINITE for a NaN or infinite coordinate.  stats (HOST, may be NULL) receives {occupied grid
+ * cells, lanes that scanned the second shell, points answered by the wave-per-query fallback}.  Waits on `stream` a few times
+ * (the grid's cell counts, the fallback count). */
+int gsr_mean_dist3(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, float* out_dist2,
+                   int stats[3], void* stream);
+/* The same with the measuring knobs: cell_target = points per occupied grid cell the build aims at (0 = the library's default,
+ * at most 64; the result does not depend on it); stage_ms (HOST, may be NULL) receives the GPU milliseconds of {grid build,
+ * lane-per-point query, fallback including the host's read of its count} from HIP events on `stream`. */
+int gsr_mean_dist3_ex(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, float* out_dist2,
+                      int cell_target, int stats[3], float stage_ms[3], void* stream);
+
+/* create_from_attribute, one lane per point, f32 throughout.  xyz_out = xyz; f_dc = (rgb - 0.5f) / C0, rgb = 1 when NULL;
+ * scale = scale_in, or when that is NULL all three axes float(log(double(sqrtf(dist2[i] + 1e-7f)))) (exactly one of dist2 /
+ * scale_in is given); rot = rot_in, or rotmat2quaternion(normal2rotation(normals)) in gsr_mesh_seeds' arithmetic with one
+ * x / max(|x|, 1e-12), or (1, 0, 0, 0) when both are NULL (both given: GSR_ERR_ARG); opacity_out = opacity_in [n], or the scalar
+ * `opacity` when NULL.  Inputs [n,3] ([n,4] rot_in); outputs xyz_out / f_dc / scale [n,3], rot [n,4], opacity_out [n].  No wait. */
+int gsr_point_seeds(const float* xyz, const float* rgb, const float* dist2, const float* scale_in, const float* rot_in,
+                    const float* normals, const float* opacity_in, float opacity, int num_points, float* xyz_out, float* f_dc,
+                    float* scale, float* rot, float* opacity_out, void* stream);
+
+/* One frame of DepthInitializer (gaustudio/pipelines/initializers/depth.py:50-89) without its files: per pixel
+ * xyz = float(half(points)); rgb = float(uint8(half(half(image) * 255))) / 255.0f (colours in [0, 1]; negative or NaN ones are
+ * outside the contract); scale (three equal axes) = float(half(float(log(double(s))))), s = float(half(depth / focal)), focal =
+ * (fx + fy) / 2 in f32: a depth of 0 gives -inf.  points / image [n,3], depth [n]; outputs [n,3].  No wait. */
+int gsr_depth_seed_pack(const float* points, const float* image, const float* depth, int num_pixels, float focal, float* xyz,
+                        float* rgb, float* scale, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

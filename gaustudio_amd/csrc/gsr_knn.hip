@@ -380,17 +380,6 @@ __global__ void __launch_bounds__(256) dist3_fold(const double* __restrict__ d2,
 }
 
 // ------------------------------------------------------------------------------------------------------ host helpers
-struct Arena {   // bump allocation out of one workspace block
-	char* p;
-	size_t off;
-	template <class T> T* take(size_t n)
-	{
-		T* r = reinterpret_cast<T*>(p + off);
-		off += (n * sizeof(T) + 255) & ~(size_t)255;
-		return r;
-	}
-};
-
 uint64_t table_size(int n)
 {
 	uint64_t s = 64;
@@ -398,50 +387,43 @@ uint64_t table_size(int n)
 	return s;
 }
 
-size_t knn_bytes(int n, int nq, int k, bool want_out)
-{
-	const uint64_t T = table_size(n);
-	size_t b = 0;
-	auto add = [&](size_t x) { b += (x + 255) & ~(size_t)255; };
-	add(T * 8); add(T * 4); add(T * 4); add(T * 4);   // keys, cnt, start, fill
-	add((size_t)n * 4); add((size_t)n * 4); add((size_t)n * 16); add(64);   // pslot, cells, sorted points, counters
-	if (want_out) { add((size_t)nq * k * 8); add((size_t)nq * k * 8); }
-	return b;
-}
-
-#define KN_TRY(expr) do { if ((expr) != hipSuccess) return GSR_ERR_HIP; } while (0)
-
-// the hashed grid over `pts`, carved out of `ws` (knn_bytes(n, .., false)) by grid_build
+// the hashed grid over `pts`: its buffers (grid_take) and what grid_build finds
 struct GridBufs {
 	Grid g;
 	unsigned long long* keys;
-	int *cnt, *start, *cells;
+	int *cnt, *start, *fill, *pslot, *cells;
 	float4* spts;
 	int* counters;   // [0..2] the build's, [3] a query that is not finite, [4..6] dist3_query's, [8..14] the bounding box
 	int occupied, ncells;
 };
-
-// builds the grid with ~m_target points per occupied cell (and no more than CELL_MAX cells along an axis)
-int grid_build(Arena& ws, const float* pts, int n, double m_target, GridBufs& gb, hipStream_t s)
+void grid_take(Arena& ws, int n, GridBufs& gb)
 {
 	const uint64_t T = table_size(n);
-	unsigned long long* keys = ws.take<unsigned long long>(T);
-	int* cnt = ws.take<int>(T);
-	int* start = ws.take<int>(T);
-	int* fill = ws.take<int>(T);
-	int* pslot = ws.take<int>(n);
-	int* cells = ws.take<int>(n);
-	float4* spts = ws.take<float4>(n);
-	int* counters = ws.take<int>(16);
+	gb.keys = ws.take<unsigned long long>(T);
+	gb.cnt = ws.take<int>(T);
+	gb.start = ws.take<int>(T);
+	gb.fill = ws.take<int>(T);
+	gb.pslot = ws.take<int>(n);
+	gb.cells = ws.take<int>(n);
+	gb.spts = ws.take<float4>(n);
+	gb.counters = ws.take<int>(16);
+}
+
+// builds the grid with ~m_target points per occupied cell (and no more than CELL_MAX cells along an axis)
+int grid_build(GridBufs& gb, const float* pts, int n, double m_target, hipStream_t s)
+{
+	const uint64_t T = table_size(n);
+	unsigned long long* keys = gb.keys;
+	int *cnt = gb.cnt, *start = gb.start, *fill = gb.fill, *pslot = gb.pslot, *cells = gb.cells, *counters = gb.counters;
 
 	int bbox_init[7] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0};
-	KN_TRY(hipMemcpyAsync(counters + 8, bbox_init, sizeof(bbox_init), hipMemcpyHostToDevice, s));
+	GSR_TRY(hipMemcpyAsync(counters + 8, bbox_init, sizeof(bbox_init), hipMemcpyHostToDevice, s));
 	const int nb = (n + 255) / 256;
 	hipLaunchKernelGGL(bbox_kernel, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, s, pts, n, counters + 8);
-	KN_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	int bbox[7];
-	KN_TRY(hipMemcpyAsync(bbox, counters + 8, sizeof(bbox), hipMemcpyDeviceToHost, s));
-	KN_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemcpyAsync(bbox, counters + 8, sizeof(bbox), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
 	if (bbox[6]) return GSR_ERR_NONFINITE;
 	double lo[3], ext = 0.0;
 	for (int a = 0; a < 3; a++) {
@@ -454,24 +436,24 @@ int grid_build(Arena& ws, const float* pts, int n, double m_target, GridBufs& gb
 	int occupied = 0;
 	for (int it = 0;; it++) {
 		g.h = h; g.inv_h = 1.0 / h; g.margin = 1e-6 * h;
-		KN_TRY(hipMemsetAsync(keys, 0xff, T * 8, s));
-		KN_TRY(hipMemsetAsync(cnt, 0, T * 4, s));
-		KN_TRY(hipMemsetAsync(counters, 0, 8 * sizeof(int), s));
+		GSR_TRY(hipMemsetAsync(keys, 0xff, T * 8, s));
+		GSR_TRY(hipMemsetAsync(cnt, 0, T * 4, s));
+		GSR_TRY(hipMemsetAsync(counters, 0, 8 * sizeof(int), s));
 		hipLaunchKernelGGL(grid_insert, dim3(nb), dim3(256), 0, s, pts, n, g, keys, pslot, cnt, counters);
-		KN_TRY(hipGetLastError());
-		KN_TRY(hipMemcpyAsync(&occupied, counters, sizeof(int), hipMemcpyDeviceToHost, s));
-		KN_TRY(hipStreamSynchronize(s));
+		GSR_TRY(hipGetLastError());
+		GSR_TRY(hipMemcpyAsync(&occupied, counters, sizeof(int), hipMemcpyDeviceToHost, s));
+		GSR_TRY(hipStreamSynchronize(s));
 		const double ratio = m_target / ((double)n / (double)(occupied > 0 ? occupied : 1));
 		if (it >= 7 || ext == 0.0 || (ratio >= 0.5 && ratio <= 2.0) || (ratio < 1.0 && h <= h_min)) break;
 		h = fmax(h * fmin(fmax(pow(ratio, 1.0 / 2.5), 1.0 / 16.0), 16.0), h_min);
 	}
-	KN_TRY(hipMemsetAsync(fill, 0, T * 4, s));
+	GSR_TRY(hipMemsetAsync(fill, 0, T * 4, s));
 	hipLaunchKernelGGL(grid_offsets, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, keys, cnt, T, start, cells, counters);
-	hipLaunchKernelGGL(grid_scatter, dim3(nb), dim3(256), 0, s, pts, n, pslot, start, fill, spts);
+	hipLaunchKernelGGL(grid_scatter, dim3(nb), dim3(256), 0, s, pts, n, pslot, start, fill, gb.spts);
 	int ncells = 0;
-	KN_TRY(hipMemcpyAsync(&ncells, counters + 2, sizeof(int), hipMemcpyDeviceToHost, s));
-	KN_TRY(hipStreamSynchronize(s));
-	gb = GridBufs{g, keys, cnt, start, cells, spts, counters, occupied, ncells};
+	GSR_TRY(hipMemcpyAsync(&ncells, counters + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
+	gb.g = g; gb.occupied = occupied; gb.ncells = ncells;
 	return GSR_OK;
 }
 
@@ -481,29 +463,23 @@ int knn_answer(const GridBufs& gb, const float* queries, int nq, int k, double* 
 	if (nq > 0)   // counters[3] (zeroed with the grid's counters): set by a query that is not finite
 		hipLaunchKernelGGL(knn_query, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, gb.g, gb.keys, gb.start, gb.cnt, gb.cells, gb.ncells,
 		                   gb.spts, queries, nq, k, dist2, idx, gb.counters + 3);
-	KN_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	if (nq > 0 && check_queries) {
 		int qbad = 0;
-		KN_TRY(hipMemcpyAsync(&qbad, gb.counters + 3, sizeof(int), hipMemcpyDeviceToHost, s));
-		KN_TRY(hipStreamSynchronize(s));
+		GSR_TRY(hipMemcpyAsync(&qbad, gb.counters + 3, sizeof(int), hipMemcpyDeviceToHost, s));
+		GSR_TRY(hipStreamSynchronize(s));
 		if (qbad) return GSR_ERR_NONFINITE_QUERY;
 	}
 	return GSR_OK;
 }
 
-// builds the grid over `pts` in `ws` and answers the queries; ws must hold knn_bytes(n, .., false)
-int knn_run(Arena& ws, const float* pts, int n, const float* queries, int nq, int k, double* dist2, int64_t* idx,
+// builds the grid over `pts` in gb's buffers (grid_take(.., n, ..)) and answers the queries
+int knn_run(GridBufs& gb, const float* pts, int n, const float* queries, int nq, int k, double* dist2, int64_t* idx,
             hipStream_t s)
 {
-	GridBufs gb;
-	const int rc = grid_build(ws, pts, n, fmin(fmax(k * 0.5, 8.0), 32.0), gb, s);   // ~k/2 points per occupied cell
+	const int rc = grid_build(gb, pts, n, fmin(fmax(k * 0.5, 8.0), 32.0), s);   // ~k/2 points per occupied cell
 	if (rc) return rc;
 	return knn_answer(gb, queries, nq, k, dist2, idx, queries != pts, s);   // the points themselves were checked with the bounding box
-}
-
-char* ws_alloc(gsr_alloc_fn alloc, void* ctx, size_t bytes)
-{
-	return alloc ? alloc(ctx, bytes) : nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------------ fusion
@@ -706,8 +682,6 @@ __global__ void __launch_bounds__(256) normal_mask(const double* __restrict__ no
 	keep[i] = m < threshold ? 1 : 0;
 }
 
-unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 extern "C" {
@@ -718,9 +692,9 @@ int gsr_knn(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* poin
 	if (!queries) { queries = points; num_queries = num_points; }
 	if (!points || num_points <= 0 || num_queries < 0 || k < 1 || k > GSR_KNN_MAX_K || k > num_points) return GSR_ERR_ARG;
 	if (num_queries > 0 && (!dist2 || !indices)) return GSR_ERR_ARG;
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, knn_bytes(num_points, 0, k, false)), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	return knn_run(ws, points, num_points, queries, num_queries, k, dist2, indices, (hipStream_t)stream);
+	GridBufs gb;
+	if (!ws_carve(workspace_alloc, workspace_ctx, [&](Arena& ws) { grid_take(ws, num_points, gb); })) return GSR_ERR_ALLOC;
+	return knn_run(gb, points, num_points, queries, num_queries, k, dist2, indices, (hipStream_t)stream);
 }
 
 int gsr_mean_dist3_ex(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* points, int num_points, float* out_dist2,
@@ -729,48 +703,50 @@ int gsr_mean_dist3_ex(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const f
 	if (!points || num_points < 4 || !out_dist2 || cell_target < 0 || cell_target > 64) return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
 	const int n = num_points;
-	const size_t left_bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, knn_bytes(n, 0, 4, false) + left_bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
+	GridBufs gb;
+	int* leftover;
+	auto carve = [&](Arena& ws) { grid_take(ws, n, gb); leftover = ws.take<int>(n); };
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	if (stage_ms)
-		for (int j = 0; j < 4; j++) KN_TRY(hipEventCreate(&ev[j]));
+		for (int j = 0; j < 4; j++) GSR_TRY(hipEventCreate(&ev[j]));
 	struct EventGuard {
 		hipEvent_t* e;
 		~EventGuard() { for (int j = 0; j < 4; j++) if (e[j]) (void)hipEventDestroy(e[j]); }
 	} guard{ev};
-	if (stage_ms) KN_TRY(hipEventRecord(ev[0], s));
-	GridBufs gb;
-	int rc = grid_build(ws, points, n, cell_target ? (double)cell_target : (double)DIST3_CELL_TARGET, gb, s);
+	if (stage_ms) GSR_TRY(hipEventRecord(ev[0], s));
+	int rc = grid_build(gb, points, n, cell_target ? (double)cell_target : (double)DIST3_CELL_TARGET, s);
 	if (rc) return rc;
-	int* leftover = ws.take<int>(n);
 	int* stat = gb.counters + 4;   // zeroed with the grid's counters
-	if (stage_ms) KN_TRY(hipEventRecord(ev[1], s));
+	if (stage_ms) GSR_TRY(hipEventRecord(ev[1], s));
 	hipLaunchKernelGGL(dist3_query, dim3(blocks(n)), dim3(256), 0, s, gb.g, gb.keys, gb.start, gb.cnt, gb.spts, n, out_dist2, leftover, stat);
-	KN_TRY(hipGetLastError());
-	if (stage_ms) KN_TRY(hipEventRecord(ev[2], s));
+	GSR_TRY(hipGetLastError());
+	if (stage_ms) GSR_TRY(hipEventRecord(ev[2], s));
 	int st[2] = {0, 0};
-	KN_TRY(hipMemcpyAsync(st, stat, sizeof(st), hipMemcpyDeviceToHost, s));
-	KN_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemcpyAsync(st, stat, sizeof(st), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
 	const int m = st[1];
 	if (m < 0 || m > n) return GSR_ERR_HIP;
 	if (m > 0) {   // far outliers, sparse regions, n close to 4: the wave-per-query search, which scans every occupied cell
-		auto r = [](size_t x) { return (x + 255) & ~(size_t)255; };
-		Arena w2{ws_alloc(workspace_alloc, workspace_ctx, r((size_t)m * 12) + 2 * r((size_t)m * 32)), 0};
-		if (!w2.p) return GSR_ERR_ALLOC;
-		float* q = w2.take<float>((size_t)m * 3);
-		double* d2 = w2.take<double>((size_t)m * 4);
-		int64_t* nbr = w2.take<int64_t>((size_t)m * 4);
+		float* q;
+		double* d2;
+		int64_t* nbr;
+		auto carve2 = [&](Arena& w2) {
+			q = w2.take<float>((size_t)m * 3);
+			d2 = w2.take<double>((size_t)m * 4);
+			nbr = w2.take<int64_t>((size_t)m * 4);
+		};
+		if (!ws_carve(workspace_alloc, workspace_ctx, carve2)) return GSR_ERR_ALLOC;
 		hipLaunchKernelGGL(gather_points, dim3(blocks(m)), dim3(256), 0, s, points, leftover, m, q);
 		rc = knn_answer(gb, q, m, 4, d2, nbr, false, s);
 		if (rc) return rc;
 		hipLaunchKernelGGL(dist3_fold, dim3(blocks(m)), dim3(256), 0, s, d2, leftover, m, out_dist2);
-		KN_TRY(hipGetLastError());
+		GSR_TRY(hipGetLastError());
 	}
 	if (stage_ms) {
-		KN_TRY(hipEventRecord(ev[3], s));
-		KN_TRY(hipEventSynchronize(ev[3]));
-		for (int j = 0; j < 3; j++) KN_TRY(hipEventElapsedTime(&stage_ms[j], ev[j], ev[j + 1]));
+		GSR_TRY(hipEventRecord(ev[3], s));
+		GSR_TRY(hipEventSynchronize(ev[3]));
+		for (int j = 0; j < 3; j++) GSR_TRY(hipEventElapsedTime(&stage_ms[j], ev[j], ev[j + 1]));
 	}
 	if (stats) { stats[0] = gb.occupied; stats[1] = st[0]; stats[2] = m; }
 	return GSR_OK;
@@ -800,42 +776,26 @@ int gsr_fusion_group(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const in
 	if (!records || num_records < 0 || num_gaussians <= 0 || !unique_ids || !mean_normals) return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
 	const int n = num_records;
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const long long nh = 256LL * ntiles;
-	const int nscan = (int)(nh > n + 1 ? nh : n + 1);
-	size_t bytes = 0;
-	auto add = [&](size_t x) { bytes += (x + 255) & ~(size_t)255; };
-	for (int j = 0; j < 4; j++) add((size_t)n * 4);             // keys / vals ping-pong
-	add((size_t)nh * 4); add(((size_t)nh + 1) * 4);             // histogram and its scan
-	add(((size_t)nscan / 1024 + 2) * 4);                        // scan partials
-	add((size_t)n * 4); add(((size_t)n + 1) * 4); add(((size_t)n + 1) * 4);   // flags, their scan, segments
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* k0 = ws.take<int>(n); int* v0 = ws.take<int>(n); int* k1 = ws.take<int>(n); int* v1 = ws.take<int>(n);
-	int* hist = ws.take<int>(nh); int* offs = ws.take<int>(nh + 1);
-	int* part = ws.take<int>(nscan / 1024 + 2);
-	int* flags = ws.take<int>(n); int* uidx = ws.take<int>(n + 1); int* seg = ws.take<int>(n + 1);
+	int *k0, *v0, *flags, *uidx, *seg;
+	SortBufs<int> sb;   // sb.part serves the scan of the flags too
+	auto carve = [&](Arena& ws) {
+		k0 = ws.take<int>(n); v0 = ws.take<int>(n); sb = sort_take<int>(ws, n, (long long)n + 1);
+		flags = ws.take<int>(n); uidx = ws.take<int>((size_t)n + 1); seg = ws.take<int>((size_t)n + 1);   // flags, their scan, segments
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 
 	hipLaunchKernelGGL(sort_init, dim3(blocks(n)), dim3(256), 0, s, records, n, k0, v0);
-	int bits = 1;
-	while (bits < 31 && (1LL << bits) < num_gaussians) bits++;
-	for (int shift = 0; shift < bits; shift += 8) {
-		hipLaunchKernelGGL(radix_hist<int>, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, hist);
-		const int rc = exclusive_scan(hist, (int)nh, offs, part, s);
-		if (rc) return rc;
-		hipLaunchKernelGGL(radix_scatter<int>, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, offs, k1, v1);
-		int* t = k0; k0 = k1; k1 = t;
-		t = v0; v0 = v1; v1 = t;
-	}
+	int rc = radix_sort(k0, v0, n, bits_for(num_gaussians), sb, s);
+	if (rc) return rc;
 	hipLaunchKernelGGL(unique_flags, dim3(blocks(n)), dim3(256), 0, s, k0, n, flags);
-	int rc = exclusive_scan(flags, n, uidx, part, s);
+	rc = exclusive_scan(flags, n, uidx, sb.part, s);
 	if (rc) return rc;
 	hipLaunchKernelGGL(unique_emit, dim3(blocks(n)), dim3(256), 0, s, k0, n, flags, uidx, seg, unique_ids);
 	int U = 0;
-	KN_TRY(hipMemcpyAsync(&U, uidx + n, sizeof(int), hipMemcpyDeviceToHost, s));
-	KN_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemcpyAsync(&U, uidx + n, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
 	hipLaunchKernelGGL(fusion_reduce, dim3(blocks(U)), dim3(256), 0, s, records, v0, seg, U, consistency, mean_normals);
-	KN_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return U;
 }
 
@@ -846,14 +806,19 @@ int gsr_fusion_smooth(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const f
 		return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
 	const int U = num_unique;
-	const size_t extra = (((size_t)U * 12 + 255) & ~(size_t)255) + 2 * (((size_t)U * k * 8 + 255) & ~(size_t)255);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, knn_bytes(U, 0, k, false) + extra), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	float* q = ws.take<float>((size_t)U * 3);
-	double* d2 = ws.take<double>((size_t)U * k);
-	int64_t* nbr = ws.take<int64_t>((size_t)U * k);
+	float* q;
+	double* d2;
+	int64_t* nbr;
+	GridBufs gb;
+	auto carve = [&](Arena& ws) {
+		q = ws.take<float>((size_t)U * 3);
+		d2 = ws.take<double>((size_t)U * k);
+		nbr = ws.take<int64_t>((size_t)U * k);
+		grid_take(ws, U, gb);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 	hipLaunchKernelGGL(gather_points, dim3(blocks(U)), dim3(256), 0, s, xyz, unique_ids, U, q);
-	const int rc = knn_run(ws, q, U, q, U, k, d2, nbr, s);
+	const int rc = knn_run(gb, q, U, q, U, k, d2, nbr, s);
 	if (rc) return rc;
 	hipLaunchKernelGGL(fusion_smooth, dim3(blocks(U)), dim3(256), 0, s, mean_normals, d2, nbr, U, k, (double)sigma, normals);
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
@@ -867,17 +832,21 @@ int gsr_outlier_statistical(gsr_alloc_fn workspace_alloc, void* workspace_ctx, c
 	hipStream_t s = (hipStream_t)stream;
 	const int n = num_points, k = nb_neighbors < n ? nb_neighbors : n;
 	const int np = (n + 255) / 256;
-	auto r = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t extra = 2 * r((size_t)n * k * 8) + r((size_t)n * 8) + r((size_t)np * 8) + r((size_t)np * 4) + r(16);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, knn_bytes(n, 0, k, false) + extra), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	double* d2 = ws.take<double>((size_t)n * k);
-	int64_t* nbr = ws.take<int64_t>((size_t)n * k);
-	double* a = ws.take<double>(n);
-	double* psum = ws.take<double>(np);
-	int* pcnt = ws.take<int>(np);
-	double* stats = ws.take<double>(2);
-	int rc = knn_run(ws, points, n, points, n, k, d2, nbr, s);
+	double *d2, *a, *psum, *stats;
+	int64_t* nbr;
+	int* pcnt;
+	GridBufs gb;
+	auto carve = [&](Arena& ws) {
+		d2 = ws.take<double>((size_t)n * k);
+		nbr = ws.take<int64_t>((size_t)n * k);
+		a = ws.take<double>(n);
+		psum = ws.take<double>(np);
+		pcnt = ws.take<int>(np);
+		stats = ws.take<double>(2);
+		grid_take(ws, n, gb);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	int rc = knn_run(gb, points, n, points, n, k, d2, nbr, s);
 	if (rc) return rc;
 	hipLaunchKernelGGL(mean_knn_dist, dim3(np), dim3(256), 0, s, d2, n, k, a);
 	hipLaunchKernelGGL(stat_partials, dim3(np), dim3(256), 0, s, a, n, stats, 1, psum, pcnt);
@@ -885,7 +854,7 @@ int gsr_outlier_statistical(gsr_alloc_fn workspace_alloc, void* workspace_ctx, c
 	hipLaunchKernelGGL(stat_partials, dim3(np), dim3(256), 0, s, a, n, stats, 2, psum, pcnt);
 	hipLaunchKernelGGL(stat_final, dim3(1), dim3(256), 0, s, psum, pcnt, np, 2, std_ratio, stats);
 	hipLaunchKernelGGL(stat_mask, dim3(np), dim3(256), 0, s, a, n, stats, keep);
-	if (mean_distance) KN_TRY(hipMemcpyAsync(mean_distance, a, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+	if (mean_distance) GSR_TRY(hipMemcpyAsync(mean_distance, a, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
 
@@ -896,12 +865,16 @@ int gsr_outlier_normal(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const 
 	if (!points || !normals || num_points < 0 || !keep || nb_neighbors < 1 || nb_neighbors > GSR_KNN_MAX_K) return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
 	const int n = num_points, k = nb_neighbors < n ? nb_neighbors : n;
-	const size_t extra = 2 * (((size_t)n * k * 8 + 255) & ~(size_t)255);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, knn_bytes(n, 0, k, false) + extra), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	double* d2 = ws.take<double>((size_t)n * k);
-	int64_t* nbr = ws.take<int64_t>((size_t)n * k);
-	const int rc = knn_run(ws, points, n, points, n, k, d2, nbr, s);
+	double* d2;
+	int64_t* nbr;
+	GridBufs gb;
+	auto carve = [&](Arena& ws) {
+		d2 = ws.take<double>((size_t)n * k);
+		nbr = ws.take<int64_t>((size_t)n * k);
+		grid_take(ws, n, gb);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	const int rc = knn_run(gb, points, n, points, n, k, d2, nbr, s);
 	if (rc) return rc;
 	hipLaunchKernelGGL(normal_mask, dim3(blocks(n)), dim3(256), 0, s, normals, nbr, n, k, angle_threshold, keep);
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;

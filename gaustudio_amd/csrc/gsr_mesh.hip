@@ -41,7 +41,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
 #include "../../include/gsrast.h"
 #include "gsr_sort.h"
@@ -53,21 +52,6 @@ constexpr int MAX_DIM = 16384;          // width / height limit: at most 1024 x 
 constexpr float KEY_SHRINK = 1.0f - 1.0f / 65536.0f;
 constexpr float KEY_GROW = 1.0f + 1.0f / 65536.0f;
 
-struct Arena {   // bump allocation out of one workspace block
-	char* p;
-	size_t off;
-	template <class T> T* take(size_t n)
-	{
-		T* r = reinterpret_cast<T*>(p + off);
-		off += (n * sizeof(T) + 255) & ~(size_t)255;
-		return r;
-	}
-};
-struct Sizer {
-	size_t bytes = 0;
-	template <class T> void add(size_t n) { bytes += (n * sizeof(T) + 255) & ~(size_t)255; }
-};
-
 struct Cam {
 	float r[12];            // row-major [R | t] of the world-to-camera matrix
 	float fx, fy, cx, cy;
@@ -75,8 +59,6 @@ struct Cam {
 	int W, H, tiles_x, tiles_y;
 	int cull;
 };
-
-unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 
 __device__ __forceinline__ float3 cross3(float3 u, float3 v)
 {
@@ -195,53 +177,6 @@ __global__ void __launch_bounds__(256) face_setup(const float4* __restrict__ vc,
 	rec[3 * (size_t)f] = make_float4(ea.x, ea.y, ea.z, eb.x);
 	rec[3 * (size_t)f + 1] = make_float4(eb.y, eb.z, ec.x, ec.y);
 	rec[3 * (size_t)f + 2] = make_float4(ec.z, a.z, b.z, c.z);
-}
-
-int scan_part_len(long long n) { return (int)(n / 1024 + 2); }
-
-// ------------------------------------------------------------------------------------------------------ stable radix sort (gsr_sort.h)
-struct SortBufs {
-	uint64_t* k1;
-	int* v1;
-	int* hist;
-	int* offs;
-	int* part;
-};
-void sort_reserve(Sizer& z, int n)
-{
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const long long nh = 256LL * ntiles;
-	z.add<uint64_t>(n); z.add<int>(n); z.add<int>(nh); z.add<int>(nh + 1); z.add<int>(scan_part_len(nh));
-}
-SortBufs sort_take(Arena& ws, int n)
-{
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const long long nh = 256LL * ntiles;
-	SortBufs b;
-	b.k1 = ws.take<uint64_t>(n); b.v1 = ws.take<int>(n); b.hist = ws.take<int>(nh); b.offs = ws.take<int>(nh + 1);
-	b.part = ws.take<int>(scan_part_len(nh));
-	return b;
-}
-// sorts (k0, v0) by the low `bits` bits of the keys, stably; the result ends up in k0 / v0 or in the SortBufs (returned)
-int radix_sort(uint64_t*& k0, int*& v0, int n, int bits, SortBufs& b, hipStream_t s)
-{
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const int nh = 256 * ntiles;
-	for (int shift = 0; shift < bits; shift += 8) {
-		hipLaunchKernelGGL(radix_hist<uint64_t>, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, b.hist);
-		const int rc = exclusive_scan<int>(b.hist, nh, b.offs, b.part, s);
-		if (rc) return rc;
-		hipLaunchKernelGGL(radix_scatter<uint64_t>, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, b.offs, b.k1, b.v1);
-		uint64_t* tk = k0; k0 = b.k1; b.k1 = tk;
-		int* tv = v0; v0 = b.v1; b.v1 = tv;
-	}
-	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
-}
-int bits_for(long long n)   // bits to hold the values 0 .. n - 1
-{
-	int b = 1;
-	while (b < 62 && (1LL << b) < n) b++;
-	return b;
 }
 
 // ------------------------------------------------------------------------------------------------------ binning
@@ -412,20 +347,6 @@ __global__ void __launch_bounds__(256) visible_mark(const int* __restrict__ p2f,
 	else if (f >= 0) vis[f] = 1;
 }
 
-#define MR_TRY(expr) do { if ((expr) != hipSuccess) return GSR_ERR_HIP; } while (0)
-
-char* ws_alloc(gsr_alloc_fn alloc, void* ctx, size_t bytes)
-{
-	return alloc ? alloc(ctx, bytes) : nullptr;
-}
-int read_status(const int* status, hipStream_t s)
-{
-	int st = 0;
-	MR_TRY(hipMemcpyAsync(&st, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	MR_TRY(hipStreamSynchronize(s));
-	return st ? GSR_ERR_ARG : GSR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -455,23 +376,28 @@ int gsr_mesh_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const 
 	hipStream_t s = (hipStream_t)stream;
 
 	// pass 1: per vertex / per face setup and the tile counts
-	Sizer z1;
-	z1.add<float4>(V); z1.add<float4>(3 * (size_t)F); z1.add<int4>(F); z1.add<uint2>(F); z1.add<float>(F); z1.add<long long>(F);
-	z1.add<long long>((size_t)F + 1); z1.add<long long>(scan_part_len(F)); z1.add<int>(1); z1.add<int2>(T);
-	Arena w1{ws_alloc(workspace_alloc, workspace_ctx, z1.bytes), 0};
-	if (!w1.p) return GSR_ERR_ALLOC;
-	float4* vc = w1.take<float4>(V);
-	float4* rec = w1.take<float4>(3 * (size_t)F);
-	int4* rect = w1.take<int4>(F);
-	uint2* prect = w1.take<uint2>(F);
-	float* key = w1.take<float>(F);
-	long long* cnt = w1.take<long long>(F);
-	long long* off = w1.take<long long>((size_t)F + 1);
-	long long* part = w1.take<long long>(scan_part_len(F));
-	int* status = w1.take<int>(1);
-	int2* ranges = w1.take<int2>(T);
-	MR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
-	MR_TRY(hipMemsetAsync(ranges, 0, sizeof(int2) * T, s));
+	float4 *vc, *rec;
+	int4* rect;
+	uint2* prect;
+	float* key;
+	long long *cnt, *off, *part;
+	int* status;
+	int2* ranges;
+	auto carve1 = [&](Arena& w1) {
+		vc = w1.take<float4>(V);
+		rec = w1.take<float4>(3 * (size_t)F);
+		rect = w1.take<int4>(F);
+		prect = w1.take<uint2>(F);
+		key = w1.take<float>(F);
+		cnt = w1.take<long long>(F);
+		off = w1.take<long long>((size_t)F + 1);
+		part = w1.take<long long>(scan_part_len(F));
+		status = w1.take<int>(1);
+		ranges = w1.take<int2>(T);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve1)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
+	GSR_TRY(hipMemsetAsync(ranges, 0, sizeof(int2) * T, s));
 	long long R = 0;
 	int st = 0;
 	if (F > 0) {
@@ -479,9 +405,9 @@ int gsr_mesh_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const 
 		hipLaunchKernelGGL(face_setup, dim3(blocks(F)), dim3(256), 0, s, vc, V, faces, F, cam, rec, rect, prect, key, cnt, status);
 		const int rc = exclusive_scan<long long>(cnt, F, off, part, s);
 		if (rc) return rc;
-		MR_TRY(hipMemcpyAsync(&R, off + F, sizeof(long long), hipMemcpyDeviceToHost, s));
-		MR_TRY(hipMemcpyAsync(&st, status, sizeof(int), hipMemcpyDeviceToHost, s));
-		MR_TRY(hipStreamSynchronize(s));
+		GSR_TRY(hipMemcpyAsync(&R, off + F, sizeof(long long), hipMemcpyDeviceToHost, s));
+		GSR_TRY(hipMemcpyAsync(&st, status, sizeof(int), hipMemcpyDeviceToHost, s));
+		GSR_TRY(hipStreamSynchronize(s));
 		if (st) return GSR_ERR_ARG;   // a face index outside [0, num_verts)
 		if (R >= (1LL << 31) - 1) return GSR_ERR_ARG;
 	}
@@ -491,20 +417,20 @@ int gsr_mesh_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const 
 	uint64_t* k0 = nullptr;
 	int* v0 = nullptr;
 	if (n > 0) {
-		Sizer z2;
-		z2.add<uint64_t>(n); z2.add<int>(n); sort_reserve(z2, n);
-		Arena w2{ws_alloc(workspace_alloc, workspace_ctx, z2.bytes), 0};
-		if (!w2.p) return GSR_ERR_ALLOC;
-		k0 = w2.take<uint64_t>(n);
-		v0 = w2.take<int>(n);
-		SortBufs sb = sort_take(w2, n);
+		SortBufs<uint64_t> sb;
+		auto carve2 = [&](Arena& w2) {
+			k0 = w2.take<uint64_t>(n);
+			v0 = w2.take<int>(n);
+			sb = sort_take<uint64_t>(w2, n);
+		};
+		if (!ws_carve(workspace_alloc, workspace_ctx, carve2)) return GSR_ERR_ALLOC;
 		hipLaunchKernelGGL(bin_emit, dim3(blocks(F)), dim3(256), 0, s, rect, key, off, F, cam.tiles_x, k0, v0);
 		const int rc = radix_sort(k0, v0, n, 32 + bits_for(T), sb, s);
 		if (rc) return rc;
 		hipLaunchKernelGGL(tile_ranges, dim3(blocks(n)), dim3(256), 0, s, k0, n, ranges);
 	}
 	hipLaunchKernelGGL(mesh_walk, dim3(T), dim3(256), 0, s, ranges, k0, v0, rec, prect, cam, pix_to_face, zbuf, bary);
-	MR_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return n;
 }
 
@@ -515,13 +441,12 @@ int gsr_mesh_interpolate(gsr_alloc_fn workspace_alloc, void* workspace_ctx, cons
 	if (num_pixels == 0) return GSR_OK;
 	if (!pix_to_face || !bary || !out || (num_faces > 0 && !faces) || (num_verts > 0 && !attr)) return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, 256), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* status = ws.take<int>(1);
-	MR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
+	int* status;
+	if (!ws_carve(workspace_alloc, workspace_ctx, [&](Arena& ws) { status = ws.take<int>(1); })) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
 	hipLaunchKernelGGL(mesh_interp, dim3(blocks(num_pixels)), dim3(256), 0, s, faces, num_faces, pix_to_face, bary, num_pixels, attr,
 	                   num_verts, channels, out, status);
-	MR_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return read_status(status, s);
 }
 
@@ -534,20 +459,24 @@ int gsr_mesh_vertex_normals(gsr_alloc_fn workspace_alloc, void* workspace_ctx, c
 	if (num_verts == 0) return num_faces > 0 ? GSR_ERR_ARG : GSR_OK;
 	hipStream_t s = (hipStream_t)stream;
 	const int n = 3 * num_faces;
-	Sizer z;
-	z.add<int>(1); z.add<int2>(num_verts);
-	if (n > 0) { z.add<uint64_t>(n); z.add<int>(n); sort_reserve(z, n); }
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* status = ws.take<int>(1);
-	int2* ranges = ws.take<int2>(num_verts);
-	MR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
-	MR_TRY(hipMemsetAsync(ranges, 0, sizeof(int2) * num_verts, s));
+	int *status, *v0 = nullptr;
+	int2* ranges;
+	uint64_t* k0 = nullptr;
+	SortBufs<uint64_t> sb;
+	auto carve = [&](Arena& ws) {
+		status = ws.take<int>(1);
+		ranges = ws.take<int2>(num_verts);
+		if (n > 0) {
+			k0 = ws.take<uint64_t>(n);
+			v0 = ws.take<int>(n);
+			sb = sort_take<uint64_t>(ws, n);
+		}
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
+	GSR_TRY(hipMemsetAsync(ranges, 0, sizeof(int2) * num_verts, s));
 	int* corners = nullptr;
 	if (n > 0) {
-		uint64_t* k0 = ws.take<uint64_t>(n);
-		int* v0 = ws.take<int>(n);
-		SortBufs sb = sort_take(ws, n);
 		hipLaunchKernelGGL(corner_emit, dim3(blocks(n)), dim3(256), 0, s, faces, (long long)n, num_verts, k0, v0, status);
 		int rc = read_status(status, s);   // an index outside [0, num_verts): nothing is written
 		if (rc) return rc;
@@ -557,7 +486,7 @@ int gsr_mesh_vertex_normals(gsr_alloc_fn workspace_alloc, void* workspace_ctx, c
 		corners = v0;
 	}
 	hipLaunchKernelGGL(vertex_normals, dim3(blocks(num_verts)), dim3(256), 0, s, verts, num_verts, faces, ranges, corners, normals);
-	MR_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return GSR_OK;
 }
 
@@ -566,14 +495,13 @@ int gsr_mesh_visible_faces(gsr_alloc_fn workspace_alloc, void* workspace_ctx, co
 {
 	if (num_pixels < 0 || num_faces < 0 || (num_pixels > 0 && !pix_to_face) || (num_faces > 0 && !visible)) return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
-	if (num_faces > 0) MR_TRY(hipMemsetAsync(visible, 0, num_faces, s));
+	if (num_faces > 0) GSR_TRY(hipMemsetAsync(visible, 0, num_faces, s));
 	if (num_pixels == 0) return GSR_OK;
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, 256), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* status = ws.take<int>(1);
-	MR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
+	int* status;
+	if (!ws_carve(workspace_alloc, workspace_ctx, [&](Arena& ws) { status = ws.take<int>(1); })) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
 	hipLaunchKernelGGL(visible_mark, dim3(blocks(num_pixels)), dim3(256), 0, s, pix_to_face, num_pixels, num_faces, visible, status);
-	MR_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return read_status(status, s);
 }
 

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/gsrast.h"
+#include "gsr_ws.h"
 
 namespace {
 
@@ -34,8 +35,6 @@ struct View {
 	float d[3];             // the viewing axis in world space: the third row of R, normalised
 	int W, H;
 };
-
-unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 
 __device__ __forceinline__ float3 cross3(float3 u, float3 v)
 {
@@ -277,8 +276,6 @@ __global__ void __launch_bounds__(256) depth_seed_pack(const float* __restrict__
 	store3(scale, (size_t)i, make_float3(ls, ls, ls));
 }
 
-#define MB_TRY(expr) do { if ((expr) != hipSuccess) return GSR_ERR_HIP; } while (0)
-
 // [R | t], K and the viewing axis of one view; false when a value is not finite, fx or fy is 0 or the axis has no length
 bool make_view(const float* intrinsics, const float* extrinsics, int W, int H, View& vw)
 {
@@ -314,7 +311,7 @@ int gsr_mesh_bake_select(const float* verts, int num_verts, const int* faces, in
 	if (!faces || !visible || num_verts == 0 || !verts || !stamp) return GSR_ERR_ARG;
 	hipLaunchKernelGGL(bake_select, dim3(blocks(num_faces)), dim3(256), 0, (hipStream_t)stream, verts, num_verts, faces, num_faces,
 	                   visible, vw, seq, stamp, cos_out);
-	MB_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return GSR_OK;
 }
 
@@ -333,7 +330,7 @@ int gsr_mesh_bake_sample(const float* verts, int num_verts, const int* stamp, in
 		hipLaunchKernelGGL(bake_sample<true>, dim3(blocks(num_verts)), dim3(256), 0, s, verts, num_verts, stamp, seq, vw, image, colors, baked_by);
 	else
 		hipLaunchKernelGGL(bake_sample<false>, dim3(blocks(num_verts)), dim3(256), 0, s, verts, num_verts, stamp, seq, vw, image, colors, baked_by);
-	MB_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return GSR_OK;
 }
 
@@ -368,17 +365,13 @@ int gsr_mesh_seeds(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const floa
 	tb.c0 = (float)0.28209479177387814;
 	tb.n = n_per_triangle;
 	hipStream_t s = (hipStream_t)stream;
-	char* ws = workspace_alloc ? workspace_alloc(workspace_ctx, 256) : nullptr;
-	if (!ws) return GSR_ERR_ALLOC;
-	int* status = reinterpret_cast<int*>(ws);
-	MB_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
+	int* status;
+	if (!ws_carve(workspace_alloc, workspace_ctx, [&](Arena& ws) { status = ws.take<int>(1); })) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
 	hipLaunchKernelGGL(mesh_seeds, dim3(blocks(P)), dim3(256), 0, s, verts, normals, vertex_colors, num_verts, faces, P, tb, xyz, f_dc,
 	                   scale, rot, status);
-	MB_TRY(hipGetLastError());
-	int st = 0;
-	MB_TRY(hipMemcpyAsync(&st, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	MB_TRY(hipStreamSynchronize(s));
-	return st ? GSR_ERR_ARG : GSR_OK;
+	GSR_TRY(hipGetLastError());
+	return read_status(status, s);
 }
 
 int gsr_point_seeds(const float* xyz, const float* rgb, const float* dist2, const float* scale_in, const float* rot_in,
@@ -390,7 +383,7 @@ int gsr_point_seeds(const float* xyz, const float* rgb, const float* dist2, cons
 	if (!xyz || (!dist2 == !scale_in) || !xyz_out || !f_dc || !scale || !rot || !opacity_out) return GSR_ERR_ARG;
 	hipLaunchKernelGGL(point_seeds, dim3(blocks(num_points)), dim3(256), 0, (hipStream_t)stream, xyz, rgb, dist2, scale_in, rot_in,
 	                   normals, opacity_in, opacity, (float)0.28209479177387814, num_points, xyz_out, f_dc, scale, rot, opacity_out);
-	MB_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return GSR_OK;
 }
 
@@ -402,7 +395,7 @@ int gsr_depth_seed_pack(const float* points, const float* image, const float* de
 	if (!points || !image || !depth || !xyz || !rgb || !scale) return GSR_ERR_ARG;
 	hipLaunchKernelGGL(depth_seed_pack, dim3(blocks(num_pixels)), dim3(256), 0, (hipStream_t)stream, points, image, depth, num_pixels,
 	                   focal, xyz, rgb, scale);
-	MB_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return GSR_OK;
 }
 

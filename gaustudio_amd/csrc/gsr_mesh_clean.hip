@@ -36,7 +36,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
 #include "../../include/gsrast.h"
 #include "gsr_sort.h"
@@ -46,69 +45,6 @@ namespace {
 constexpr int CC_BATCH = 4;          // rounds enqueued between two reads of the "changed" words
 constexpr int CC_MAX_ROUNDS = 4096;  // never reached (FastSV needs O(log F) rounds); a bound on the host loop
 constexpr int AREA_PIECE = 1024;     // triangles per partial sum
-
-struct Arena {   // bump allocation out of one workspace block
-	char* p;
-	size_t off;
-	template <class T> T* take(size_t n)
-	{
-		T* r = reinterpret_cast<T*>(p + off);
-		off += (n * sizeof(T) + 255) & ~(size_t)255;
-		return r;
-	}
-};
-struct Sizer {
-	size_t bytes = 0;
-	template <class T> void add(size_t n) { bytes += (n * sizeof(T) + 255) & ~(size_t)255; }
-};
-
-unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
-int scan_part_len(long long n) { return (int)(n / 1024 + 2); }
-int bits_for(long long n)   // bits to hold the values 0 .. n - 1
-{
-	int b = 1;
-	while (b < 62 && (1LL << b) < n) b++;
-	return b;
-}
-
-// ------------------------------------------------------------------------------------------------------ stable radix sort (gsr_sort.h)
-struct SortBufs {
-	uint64_t* k1;
-	int* v1;
-	int* hist;
-	int* offs;
-	int* part;
-};
-void sort_reserve(Sizer& z, int n)
-{
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const long long nh = 256LL * ntiles;
-	z.add<uint64_t>(n); z.add<int>(n); z.add<int>(nh); z.add<int>(nh + 1); z.add<int>(scan_part_len(nh));
-}
-SortBufs sort_take(Arena& ws, int n)
-{
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const long long nh = 256LL * ntiles;
-	SortBufs b;
-	b.k1 = ws.take<uint64_t>(n); b.v1 = ws.take<int>(n); b.hist = ws.take<int>(nh); b.offs = ws.take<int>(nh + 1);
-	b.part = ws.take<int>(scan_part_len(nh));
-	return b;
-}
-// sorts (k0, v0) by the low `bits` bits of the keys, stably; the result ends up in k0 / v0 or in the SortBufs (returned)
-int radix_sort(uint64_t*& k0, int*& v0, int n, int bits, SortBufs& b, hipStream_t s)
-{
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const int nh = 256 * ntiles;
-	for (int shift = 0; shift < bits; shift += 8) {
-		hipLaunchKernelGGL(radix_hist<uint64_t>, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, b.hist);
-		const int rc = exclusive_scan<int>(b.hist, nh, b.offs, b.part, s);
-		if (rc) return rc;
-		hipLaunchKernelGGL(radix_scatter<uint64_t>, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, b.offs, b.k1, b.v1);
-		uint64_t* tk = k0; k0 = b.k1; b.k1 = tk;
-		int* tv = v0; v0 = b.v1; b.v1 = tv;
-	}
-	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
-}
 
 // ------------------------------------------------------------------------------------------------------ union edges
 // corner i = 3 t + k holds the edge (faces[t, k], faces[t, (k + 1) % 3]) of triangle t
@@ -318,20 +254,6 @@ __global__ void __launch_bounds__(256) compact_verts(const float* __restrict__ v
 	}
 }
 
-#define MC_TRY(expr) do { if ((expr) != hipSuccess) return GSR_ERR_HIP; } while (0)
-
-char* ws_alloc(gsr_alloc_fn alloc, void* ctx, size_t bytes)
-{
-	return alloc ? alloc(ctx, bytes) : nullptr;
-}
-int read_status(const int* status, hipStream_t s)
-{
-	int st = 0;
-	MC_TRY(hipMemcpyAsync(&st, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	MC_TRY(hipStreamSynchronize(s));
-	return st ? GSR_ERR_ARG : GSR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -347,27 +269,27 @@ int gsr_mesh_cluster_triangles(gsr_alloc_fn workspace_alloc, void* workspace_ctx
 	const int F = num_faces, n = 3 * F;
 	const int vbits = bits_for(num_verts);
 
-	Sizer z;
-	z.add<int>(1 + CC_BATCH); z.add<uint64_t>(n); z.add<int>(n); sort_reserve(z, n);
-	z.add<int>(n); z.add<int>((size_t)n + 1); z.add<int>(scan_part_len(n));
-	for (int k = 0; k < 4; k++) z.add<int>(F);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* status = ws.take<int>(1 + CC_BATCH);   // [0] = a bad index, [1 ..] = the "changed" words of a batch of rounds
+	int *status, *v0, *flag, *off, *part, *f, *gf, *next, *next2;
+	uint64_t* k0;
+	SortBufs<uint64_t> sb;
+	auto carve = [&](Arena& ws) {
+		status = ws.take<int>(1 + CC_BATCH);   // [0] = a bad index, [1 ..] = the "changed" words of a batch of rounds
+		k0 = ws.take<uint64_t>(n);
+		v0 = ws.take<int>(n);
+		sb = sort_take<uint64_t>(ws, n);
+		flag = ws.take<int>(n);
+		off = ws.take<int>((size_t)n + 1);
+		part = ws.take<int>(scan_part_len(n));
+		f = ws.take<int>(F);
+		gf = ws.take<int>(F);
+		next = ws.take<int>(F);
+		next2 = ws.take<int>(F);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 	int* changed = status + 1;
-	uint64_t* k0 = ws.take<uint64_t>(n);
-	int* v0 = ws.take<int>(n);
-	SortBufs sb = sort_take(ws, n);
-	int* flag = ws.take<int>(n);
-	int* off = ws.take<int>((size_t)n + 1);
-	int* part = ws.take<int>(scan_part_len(n));
-	int* f = ws.take<int>(F);
-	int* gf = ws.take<int>(F);
-	int* next = ws.take<int>(F);
-	int* next2 = ws.take<int>(F);
 
 	// the (edge, triangle) pairs, sorted by edge; the index check before anything is written
-	MC_TRY(hipMemsetAsync(status, 0, sizeof(int) * (1 + CC_BATCH), s));
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int) * (1 + CC_BATCH), s));
 	hipLaunchKernelGGL(edge_emit, dim3(blocks(n)), dim3(256), 0, s, faces, n, num_verts, vbits, k0, v0, status);
 	int rc = read_status(status, s);
 	if (rc) return rc;
@@ -377,9 +299,9 @@ int gsr_mesh_cluster_triangles(gsr_alloc_fn workspace_alloc, void* workspace_ctx
 	rc = exclusive_scan<int>(flag, n, off, part, s);
 	if (rc) return rc;
 	int E = 0;
-	MC_TRY(hipMemcpyAsync(&E, off + n, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipMemcpyAsync(&E, off + n, sizeof(int), hipMemcpyDeviceToHost, s));
 	hipLaunchKernelGGL(cc_init, dim3(blocks(F)), dim3(256), 0, s, F, f, gf, next);
-	MC_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipStreamSynchronize(s));
 	// the sorted keys are dead from here: their first buffer holds the compacted union edges (E <= n - 1 pairs of 8 bytes)
 	// (radix_sort leaves the buffer that does not hold the result in sb.k1)
 	int2* edges = reinterpret_cast<int2*>(sb.k1);
@@ -392,15 +314,15 @@ int gsr_mesh_cluster_triangles(gsr_alloc_fn workspace_alloc, void* workspace_ctx
 	bool done = E == 0;
 	while (!done) {
 		if (nrounds >= CC_MAX_ROUNDS) return GSR_ERR_HIP;
-		MC_TRY(hipMemsetAsync(changed, 0, sizeof(int) * CC_BATCH, s));
+		GSR_TRY(hipMemsetAsync(changed, 0, sizeof(int) * CC_BATCH, s));
 		for (int r = 0; r < CC_BATCH; r++) {
 			hipLaunchKernelGGL(cc_hook, dim3(blocks(E)), dim3(256), 0, s, edges, E, f, gf, next);
 			hipLaunchKernelGGL(cc_jump, dim3(blocks(F)), dim3(256), 0, s, F, next, f, gf, next2, changed + r);
 			int* t = next; next = next2; next2 = t;
 		}
 		int ch[CC_BATCH];
-		MC_TRY(hipMemcpyAsync(ch, changed, sizeof(int) * CC_BATCH, hipMemcpyDeviceToHost, s));
-		MC_TRY(hipStreamSynchronize(s));
+		GSR_TRY(hipMemcpyAsync(ch, changed, sizeof(int) * CC_BATCH, hipMemcpyDeviceToHost, s));
+		GSR_TRY(hipStreamSynchronize(s));
 		for (int r = 0; r < CC_BATCH && !done; r++) {
 			nrounds++;
 			done = ch[r] == 0;
@@ -413,11 +335,11 @@ int gsr_mesh_cluster_triangles(gsr_alloc_fn workspace_alloc, void* workspace_ctx
 	rc = exclusive_scan<int>(flag, F, off, part, s);
 	if (rc) return rc;
 	int C = 0;
-	MC_TRY(hipMemcpyAsync(&C, off + F, sizeof(int), hipMemcpyDeviceToHost, s));
-	MC_TRY(hipStreamSynchronize(s));
-	MC_TRY(hipMemsetAsync(cluster_n_triangles, 0, sizeof(int) * (size_t)C, s));
+	GSR_TRY(hipMemcpyAsync(&C, off + F, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemsetAsync(cluster_n_triangles, 0, sizeof(int) * (size_t)C, s));
 	hipLaunchKernelGGL(cluster_assign, dim3(blocks(F)), dim3(256), 0, s, f, off, F, triangle_clusters, cluster_n_triangles);
-	MC_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return C;
 }
 
@@ -431,24 +353,27 @@ int gsr_mesh_cluster_area(gsr_alloc_fn workspace_alloc, void* workspace_ctx, con
 	const int F = num_faces, C = num_clusters;
 	const long long max_pieces = (long long)F / AREA_PIECE + C;
 
-	Sizer z;
-	z.add<int>(1); z.add<uint64_t>(F); z.add<int>(F); sort_reserve(z, F);
-	z.add<double>(F); z.add<int2>(C); z.add<int>(C); z.add<int>((size_t)C + 1); z.add<int>(scan_part_len(C)); z.add<double>(max_pieces);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* status = ws.take<int>(1);
-	uint64_t* k0 = ws.take<uint64_t>(F);
-	int* v0 = ws.take<int>(F);
-	SortBufs sb = sort_take(ws, F);
-	double* area = ws.take<double>(F);
-	int2* ranges = ws.take<int2>(C);
-	int* npieces = ws.take<int>(C);
-	int* poff = ws.take<int>((size_t)C + 1);
-	int* part = ws.take<int>(scan_part_len(C));
-	double* partial = ws.take<double>(max_pieces);
+	int *status, *v0, *npieces, *poff, *part;
+	uint64_t* k0;
+	SortBufs<uint64_t> sb;
+	double *area, *partial;
+	int2* ranges;
+	auto carve = [&](Arena& ws) {
+		status = ws.take<int>(1);
+		k0 = ws.take<uint64_t>(F);
+		v0 = ws.take<int>(F);
+		sb = sort_take<uint64_t>(ws, F);
+		area = ws.take<double>(F);
+		ranges = ws.take<int2>(C);
+		npieces = ws.take<int>(C);
+		poff = ws.take<int>((size_t)C + 1);
+		part = ws.take<int>(scan_part_len(C));
+		partial = ws.take<double>(max_pieces);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 
-	MC_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
-	MC_TRY(hipMemsetAsync(ranges, 0, sizeof(int2) * (size_t)C, s));
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
+	GSR_TRY(hipMemsetAsync(ranges, 0, sizeof(int2) * (size_t)C, s));
 	hipLaunchKernelGGL(area_emit, dim3(blocks(F)), dim3(256), 0, s, triangle_clusters, F, C, k0, v0, status);
 	int rc = radix_sort(k0, v0, F, bits_for(C), sb, s);
 	if (rc) return rc;
@@ -457,13 +382,13 @@ int gsr_mesh_cluster_area(gsr_alloc_fn workspace_alloc, void* workspace_ctx, con
 	rc = exclusive_scan<int>(npieces, C, poff, part, s);
 	if (rc) return rc;
 	int P = 0;
-	MC_TRY(hipMemcpyAsync(&P, poff + C, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipMemcpyAsync(&P, poff + C, sizeof(int), hipMemcpyDeviceToHost, s));
 	rc = read_status(status, s);   // a cluster index outside [0, num_clusters) or a face index outside [0, num_verts)
 	if (rc) return rc;
 	if (P > max_pieces) return GSR_ERR_ARG;
 	if (P > 0) hipLaunchKernelGGL(piece_sum, dim3((P + 3) / 4), dim3(256), 0, s, area, ranges, poff, C, P, partial);
 	hipLaunchKernelGGL(cluster_sum, dim3(blocks(C)), dim3(256), 0, s, partial, poff, C, cluster_area);
-	MC_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	return GSR_OK;
 }
 
@@ -479,32 +404,32 @@ int gsr_mesh_compact(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const fl
 	const int F = num_faces, V = num_verts;
 	const int m = F > V ? F : V;
 
-	Sizer z;
-	z.add<int>(1); z.add<int>(F); z.add<int>((size_t)F + 1); z.add<int>(V); z.add<int>((size_t)V + 1); z.add<int>(scan_part_len(m));
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* status = ws.take<int>(1);
-	int* fflag = ws.take<int>(F);
-	int* foff = ws.take<int>((size_t)F + 1);
-	int* vflag = ws.take<int>(V);
-	int* voff = ws.take<int>((size_t)V + 1);
-	int* part = ws.take<int>(scan_part_len(m));
+	int *status, *fflag, *foff, *vflag, *voff, *part;
+	auto carve = [&](Arena& ws) {
+		status = ws.take<int>(1);
+		fflag = ws.take<int>(F);
+		foff = ws.take<int>((size_t)F + 1);
+		vflag = ws.take<int>(V);
+		voff = ws.take<int>((size_t)V + 1);
+		part = ws.take<int>(scan_part_len(m));
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 
-	MC_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
-	MC_TRY(hipMemsetAsync(vflag, 0, sizeof(int) * (size_t)V, s));
+	GSR_TRY(hipMemsetAsync(status, 0, sizeof(int), s));
+	GSR_TRY(hipMemsetAsync(vflag, 0, sizeof(int) * (size_t)V, s));
 	hipLaunchKernelGGL(keep_mark, dim3(blocks(F)), dim3(256), 0, s, faces, keep, F, V, fflag, vflag, status);
 	int rc = exclusive_scan<int>(fflag, F, foff, part, s);
 	if (rc) return rc;
 	rc = exclusive_scan<int>(vflag, V, voff, part, s);
 	if (rc) return rc;
 	int nf = 0, nv = 0;
-	MC_TRY(hipMemcpyAsync(&nf, foff + F, sizeof(int), hipMemcpyDeviceToHost, s));
-	MC_TRY(hipMemcpyAsync(&nv, voff + V, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipMemcpyAsync(&nf, foff + F, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipMemcpyAsync(&nv, voff + V, sizeof(int), hipMemcpyDeviceToHost, s));
 	rc = read_status(status, s);   // a face index outside [0, num_verts): nothing is written
 	if (rc) return rc;
 	hipLaunchKernelGGL(compact_faces, dim3(blocks(F)), dim3(256), 0, s, faces, fflag, foff, voff, F, out_faces, face_index);
 	hipLaunchKernelGGL(compact_verts, dim3(blocks(V)), dim3(256), 0, s, verts, vflag, voff, V, out_verts, vertex_index);
-	MC_TRY(hipGetLastError());
+	GSR_TRY(hipGetLastError());
 	if (num_verts_out) *num_verts_out = nv;
 	return nf;
 }

@@ -32,34 +32,8 @@
 
 namespace {
 
-struct Arena {   // bump allocation out of one workspace block
-	char* p;
-	size_t off;
-	template <class T> T* take(size_t n)
-	{
-		T* r = reinterpret_cast<T*>(p + off);
-		off += (n * sizeof(T) + 255) & ~(size_t)255;
-		return r;
-	}
-};
-struct Sizer {
-	size_t bytes = 0;
-	template <class T> void add(size_t n) { bytes += (n * sizeof(T) + 255) & ~(size_t)255; }
-};
-
-unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 unsigned stream_blocks(long long n) { long long b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
-int scan_part_len(long long n) { return (int)(n / 1024 + 2); }
-int bits_for(long long n)   // bits to hold the values 0 .. n - 1
-{
-	int b = 1;
-	while (b < 31 && (1LL << b) < n) b++;
-	return b;
-}
-char* ws_alloc(gsr_alloc_fn alloc, void* ctx, size_t bytes) { return alloc ? alloc(ctx, bytes) : nullptr; }
 bool good_res(int r0, int r1, int r2) { return r0 >= 2 && r1 >= 2 && r2 >= 2 && (long long)r0 * r1 * r2 < (1LL << 30); }
-
-#define PSR_TRY(x) do { if ((x) != hipSuccess) return GSR_ERR_HIP; } while (0)
 
 struct Res { int r[3]; float cs[3]; float rf[3]; };
 Res make_res(int r0, int r1, int r2)
@@ -401,42 +375,29 @@ int gsr_psr_rasterize(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const f
 	const int n = num_points, C = channels;
 	const long long nn = (long long)r0 * r1 * r2;
 	const Res R = make_res(r0, r1, r2);
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const long long nh = 256LL * ntiles;
-	const long long nscan = nh > nn ? nh : nn;
-	Sizer z;
-	for (int j = 0; j < 4; j++) z.add<int>(n);
-	z.add<int>(nh); z.add<int>(nh + 1); z.add<int>(scan_part_len(nscan));
-	z.add<int>(nn); z.add<int>(nn + 1); z.add<float>((size_t)n * 3); z.add<float>((size_t)n * C); z.add<int>(1);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* k0 = ws.take<int>(n); int* v0 = ws.take<int>(n); int* k1 = ws.take<int>(n); int* v1 = ws.take<int>(n);
-	int* hist = ws.take<int>(nh); int* offs = ws.take<int>(nh + 1); int* part = ws.take<int>(scan_part_len(nscan));
-	int* cell_count = ws.take<int>(nn); int* cell_start = ws.take<int>(nn + 1);
-	float* spts = ws.take<float>((size_t)n * 3); float* svals = ws.take<float>((size_t)n * C);
-	int* status = ws.take<int>(1);
+	int *k0, *v0, *cell_count, *cell_start, *status;
+	SortBufs<int> sb;   // sb.part serves the scan of the cell counts too
+	float *spts, *svals;
+	auto carve = [&](Arena& ws) {
+		k0 = ws.take<int>(n); v0 = ws.take<int>(n); sb = sort_take<int>(ws, n, nn);
+		cell_count = ws.take<int>(nn); cell_start = ws.take<int>(nn + 1);
+		spts = ws.take<float>((size_t)n * 3); svals = ws.take<float>((size_t)n * C);
+		status = ws.take<int>(1);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 
-	PSR_TRY(hipMemsetAsync(cell_count, 0, (size_t)nn * 4, s));
-	PSR_TRY(hipMemsetAsync(status, 0, 4, s));
+	GSR_TRY(hipMemsetAsync(cell_count, 0, (size_t)nn * 4, s));
+	GSR_TRY(hipMemsetAsync(status, 0, 4, s));
 	if (n > 0) hipLaunchKernelGGL(psr_keys, dim3(blocks(n)), dim3(256), 0, s, points, n, R, k0, v0, cell_count, status);
-	int rc = exclusive_scan(cell_count, (int)nn, cell_start, part, s);
+	int rc = exclusive_scan(cell_count, (int)nn, cell_start, sb.part, s);
 	if (rc) return rc;
 	if (n > 0) {
-		const int bits = bits_for(nn);
-		for (int shift = 0; shift < bits; shift += 8) {
-			hipLaunchKernelGGL(radix_hist<int>, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, hist);
-			rc = exclusive_scan(hist, (int)nh, offs, part, s);
-			if (rc) return rc;
-			hipLaunchKernelGGL(radix_scatter<int>, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, offs, k1, v1);
-			int* t = k0; k0 = k1; k1 = t;
-			t = v0; v0 = v1; v1 = t;
-		}
+		rc = radix_sort(k0, v0, n, bits_for(nn), sb, s);
+		if (rc) return rc;
 		hipLaunchKernelGGL(psr_permute, dim3(blocks(n)), dim3(256), 0, s, points, values, n, C, v0, spts, svals);
 	}
-	int bad = 0;
-	PSR_TRY(hipMemcpyAsync(&bad, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	PSR_TRY(hipStreamSynchronize(s));
-	if (bad) return GSR_ERR_ARG;
+	rc = read_status(status, s);
+	if (rc) return rc;
 	// a valid cloud: every point has a cell count, cell_start[nn] == n, every sorted slot below it holds a valid point
 	hipLaunchKernelGGL(psr_node_gather, dim3(blocks(nn)), dim3(256), 0, s, spts, svals, C, cell_start, R, weighted, grid, counts);
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
@@ -457,20 +418,19 @@ int gsr_psr_interp(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const floa
 	if (!grid || !good_res(r0, r1, r2) || !points || num_points < 1 || !samples) return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
 	const int n = num_points, np = (int)blocks(n);
-	Sizer z;
-	z.add<double>(np); z.add<double>(1); z.add<int>(1);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	double* partial = ws.take<double>(np);
-	double* m = ws.take<double>(1);
-	int* status = ws.take<int>(1);
-	PSR_TRY(hipMemsetAsync(status, 0, 4, s));
+	double *partial, *m;
+	int* status;
+	auto carve = [&](Arena& ws) {
+		partial = ws.take<double>(np);
+		m = ws.take<double>(1);
+		status = ws.take<int>(1);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, 4, s));
 	hipLaunchKernelGGL(psr_interp, dim3(np), dim3(256), 0, s, grid, make_res(r0, r1, r2), points, n, samples, partial, status);
 	hipLaunchKernelGGL(psr_mean, dim3(1), dim3(256), 0, s, partial, np, n, mean ? mean : m);
-	int bad = 0;
-	PSR_TRY(hipMemcpyAsync(&bad, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	PSR_TRY(hipStreamSynchronize(s));
-	if (bad) return GSR_ERR_ARG;
+	const int rc = read_status(status, s);
+	if (rc) return rc;
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
 
@@ -497,19 +457,17 @@ int gsr_psr_mc_classify(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const
 	if (rc) return rc;
 	hipStream_t s = (hipStream_t)stream;
 	const long long nn = (long long)r0 * r1 * r2;
-	Sizer z;
-	z.add<int>(nn); z.add<int>(nn); z.add<int>(scan_part_len(nn));
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* nvc = ws.take<int>(nn); int* ntc = ws.take<int>(nn); int* part = ws.take<int>(scan_part_len(nn));
+	int *nvc, *ntc, *part;
+	auto carve = [&](Arena& ws) { nvc = ws.take<int>(nn); ntc = ws.take<int>(nn); part = ws.take<int>(scan_part_len(nn)); };
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 	hipLaunchKernelGGL(psr_mc_classify, dim3(blocks(nn)), dim3(256), 0, s, grid, r0, r1, r2, level, node_info, nvc, ntc);
 	rc = exclusive_scan(nvc, (int)nn, vertex_offset, part, s);
 	if (rc) return rc;
 	rc = exclusive_scan(ntc, (int)nn, triangle_offset, part, s);
 	if (rc) return rc;
-	PSR_TRY(hipMemcpyAsync(num_vertices, vertex_offset + nn, sizeof(int), hipMemcpyDeviceToHost, s));
-	PSR_TRY(hipMemcpyAsync(num_triangles, triangle_offset + nn, sizeof(int), hipMemcpyDeviceToHost, s));
-	PSR_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemcpyAsync(num_vertices, vertex_offset + nn, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipMemcpyAsync(num_triangles, triangle_offset + nn, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
 	return GSR_OK;
 }
 

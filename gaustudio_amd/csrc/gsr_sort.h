@@ -1,5 +1,7 @@
-// gsr_sort.h -- the device exclusive scan and the stable LSD radix sort shared by gsr_knn.hip (fusion records grouped by
-// Gaussian id) and gsr_mesh.hip (faces binned by tile, vertex corners grouped by vertex).  Everything here has internal
+// gsr_sort.h -- the device exclusive scan and the stable LSD radix sort (kernels, buffers and the pass loop) shared by
+// gsr_knn.hip (fusion records grouped by Gaussian id), gsr_mesh.hip (faces binned by tile, vertex corners grouped by vertex),
+// gsr_mesh_clean.hip (edges grouped by vertex pair, triangles by cluster), gsr_voxel.hip (triangle-voxel pairs by voxel) and
+// gsr_psr.hip (points by grid cell); the scan alone serves more stages of the same files.  Everything here has internal
 // linkage: each file that includes it gets its own kernels (no relocatable device code in this library).
 #ifndef GSR_SORT_H_INCLUDED
 #define GSR_SORT_H_INCLUDED
@@ -8,6 +10,7 @@
 #include <type_traits>
 
 #include "../../include/gsrast.h"
+#include "gsr_ws.h"
 
 namespace {
 
@@ -70,6 +73,7 @@ __global__ void __launch_bounds__(1024) scan_apply(const T* __restrict__ in, int
 	if (i < n) out[i] = part[blockIdx.x] + incl - v;
 	if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = part[np];
 }
+int scan_part_len(long long n) { return (int)(n / 1024 + 2); }   // elements of `part` for a scan of n values
 // out[n + 1]: exclusive scan and total
 template <class T>
 int exclusive_scan(const T* in, int n, T* out, T* part, hipStream_t s)
@@ -142,6 +146,41 @@ __global__ void __launch_bounds__(256) radix_scatter(const K* __restrict__ keys,
 		for (int w = 0; w < 4; w++) wcnt[w][threadIdx.x] = 0;
 		__syncthreads();
 	}
+}
+
+// the sort's second key / value pair, the digit-major histogram, its scan and the scan's partial sums
+template <class K>
+struct SortBufs {
+	K* k1;
+	int* v1;
+	int *hist, *offs, *part;
+};
+int sort_tiles(int n) { return (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS); }
+// the buffers for sorting n items; `part` is long enough for a scan of `scan_n` values too, for callers that reuse it
+template <class K>
+SortBufs<K> sort_take(Arena& ws, int n, long long scan_n = 0)
+{
+	const long long nh = 256LL * sort_tiles(n);
+	SortBufs<K> b;
+	b.k1 = ws.take<K>(n); b.v1 = ws.take<int>(n); b.hist = ws.take<int>(nh); b.offs = ws.take<int>(nh + 1);
+	b.part = ws.take<int>(scan_part_len(nh > scan_n ? nh : scan_n));
+	return b;
+}
+// sorts (k0, v0) by the low `bits` bits of the keys, stably, in ceil(bits / 8) passes; the result ends up in k0 / v0, which
+// trade places with b.k1 / b.v1 after every pass
+template <class K>
+int radix_sort(K*& k0, int*& v0, int n, int bits, SortBufs<K>& b, hipStream_t s)
+{
+	const int ntiles = sort_tiles(n);
+	for (int shift = 0; shift < bits; shift += 8) {
+		hipLaunchKernelGGL(radix_hist<K>, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, b.hist);
+		const int rc = exclusive_scan<int>(b.hist, 256 * ntiles, b.offs, b.part, s);
+		if (rc) return rc;
+		hipLaunchKernelGGL(radix_scatter<K>, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, b.offs, b.k1, b.v1);
+		K* tk = k0; k0 = b.k1; b.k1 = tk;
+		int* tv = v0; v0 = b.v1; b.v1 = tv;
+	}
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
 
 }  // namespace

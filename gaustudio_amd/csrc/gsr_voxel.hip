@@ -33,33 +33,6 @@
 
 namespace {
 
-struct Arena {   // bump allocation out of one workspace block
-	char* p;
-	size_t off;
-	template <class T> T* take(size_t n)
-	{
-		T* r = reinterpret_cast<T*>(p + off);
-		off += (n * sizeof(T) + 255) & ~(size_t)255;
-		return r;
-	}
-};
-struct Sizer {
-	size_t bytes = 0;
-	template <class T> void add(size_t n) { bytes += (n * sizeof(T) + 255) & ~(size_t)255; }
-};
-
-unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
-int scan_part_len(long long n) { return (int)(n / 1024 + 2); }
-int bits_for(long long n)   // bits to hold the values 0 .. n - 1
-{
-	int b = 1;
-	while (b < 31 && (1LL << b) < n) b++;
-	return b;
-}
-char* ws_alloc(gsr_alloc_fn alloc, void* ctx, size_t bytes) { return alloc ? alloc(ctx, bytes) : nullptr; }
-
-#define VOX_TRY(x) do { if ((x) != hipSuccess) return GSR_ERR_HIP; } while (0)
-
 struct VGrid { double vs, h, mb[3]; int n[3]; };
 
 bool make_grid(double voxel_size, const double* min_bound, int n0, int n1, int n2, VGrid* G)
@@ -420,26 +393,27 @@ int gsr_voxel_plan(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const doub
 		return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
 	const int nf = num_faces;
-	Sizer z;
-	z.add<int>(nf); z.add<int>(scan_part_len(nf)); z.add<unsigned long long>(1); z.add<int>(1); z.add<int>((size_t)nf * 6);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* ncol = ws.take<int>(nf); int* part = ws.take<int>(scan_part_len(nf));
-	unsigned long long* total = ws.take<unsigned long long>(1); int* status = ws.take<int>(1);
-	int* box = ws.take<int>((size_t)nf * 6);   // the caller's arrays are written only once the mesh has been found valid
-	VOX_TRY(hipMemsetAsync(total, 0, 8, s));
-	VOX_TRY(hipMemsetAsync(status, 0, 4, s));
+	int *ncol, *part, *status, *box;
+	unsigned long long* total;
+	auto carve = [&](Arena& ws) {
+		ncol = ws.take<int>(nf); part = ws.take<int>(scan_part_len(nf));
+		total = ws.take<unsigned long long>(1); status = ws.take<int>(1);
+		box = ws.take<int>((size_t)nf * 6);   // the caller's arrays are written only once the mesh has been found valid
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(total, 0, 8, s));
+	GSR_TRY(hipMemsetAsync(status, 0, 4, s));
 	if (nf > 0) {
 		hipLaunchKernelGGL(vox_check_vertices, dim3(blocks(3LL * num_vertices)), dim3(256), 0, s, vertices, 3LL * num_vertices, status);
 		hipLaunchKernelGGL(vox_plan, dim3(blocks(nf)), dim3(256), 0, s, vertices, num_vertices, faces, nf, G, box, ncol, total, status);
 	}
 	int bad = 0;
 	unsigned long long tot = 0;
-	VOX_TRY(hipMemcpyAsync(&bad, status, sizeof(int), hipMemcpyDeviceToHost, s));
-	VOX_TRY(hipMemcpyAsync(&tot, total, sizeof(tot), hipMemcpyDeviceToHost, s));
-	VOX_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemcpyAsync(&bad, status, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipMemcpyAsync(&tot, total, sizeof(tot), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
 	if (bad || tot > (unsigned long long)GSR_VOXEL_MAX_ITEMS) return GSR_ERR_ARG;
-	if (nf > 0) VOX_TRY(hipMemcpyAsync(tri_box, box, (size_t)nf * 6 * sizeof(int), hipMemcpyDeviceToDevice, s));
+	if (nf > 0) GSR_TRY(hipMemcpyAsync(tri_box, box, (size_t)nf * 6 * sizeof(int), hipMemcpyDeviceToDevice, s));
 	const int rc = exclusive_scan(ncol, nf, col_start, part, s);
 	if (rc) return rc;
 	*num_items = (int)tot;
@@ -455,21 +429,22 @@ int gsr_voxel_count(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const dou
 	    !item_start || !num_pairs || (num_items > 0 && (!vertices || !faces || !tri_box || !col_start || num_faces < 1)))
 		return GSR_ERR_ARG;
 	hipStream_t s = (hipStream_t)stream;
-	Sizer z;
-	z.add<int>(num_items); z.add<int>(scan_part_len(num_items)); z.add<unsigned long long>(1);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* count = ws.take<int>(num_items); int* part = ws.take<int>(scan_part_len(num_items));
-	unsigned long long* total = ws.take<unsigned long long>(1);
-	VOX_TRY(hipMemsetAsync(total, 0, 8, s));
+	int *count, *part;
+	unsigned long long* total;
+	auto carve = [&](Arena& ws) {
+		count = ws.take<int>(num_items); part = ws.take<int>(scan_part_len(num_items));
+		total = ws.take<unsigned long long>(1);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(total, 0, 8, s));
 	if (num_items > 0)
 		hipLaunchKernelGGL(vox_items<false>, dim3(blocks(num_items)), dim3(256), 0, s, vertices, faces, num_faces, G, tri_box, col_start,
 		                   num_items, count, (const int*)nullptr, (int*)nullptr, (int*)nullptr, total);
 	const int rc = exclusive_scan(count, num_items, item_start, part, s);
 	if (rc) return rc;
 	unsigned long long tot = 0;
-	VOX_TRY(hipMemcpyAsync(&tot, total, sizeof(tot), hipMemcpyDeviceToHost, s));
-	VOX_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemcpyAsync(&tot, total, sizeof(tot), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
 	if (tot > (unsigned long long)GSR_VOXEL_MAX_ITEMS) return GSR_ERR_ARG;
 	*num_pairs = (int)tot;
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
@@ -502,42 +477,30 @@ int gsr_voxel_sort(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const uint
 	hipStream_t s = (hipStream_t)stream;
 	const int n = num_pairs;
 	const long long nn = (long long)n0 * n1 * n2;
-	if (occupancy) VOX_TRY(hipMemsetAsync(occupancy, 0, (size_t)((nn + 31) / 32) * 4, s));
+	if (occupancy) GSR_TRY(hipMemsetAsync(occupancy, 0, (size_t)((nn + 31) / 32) * 4, s));
 	if (n == 0) {
-		VOX_TRY(hipMemsetAsync(pair_start, 0, sizeof(int), s));
+		GSR_TRY(hipMemsetAsync(pair_start, 0, sizeof(int), s));
 		*num_voxels = 0;
 		return GSR_OK;
 	}
-	const int ntiles = (n + 256 * RADIX_ITEMS - 1) / (256 * RADIX_ITEMS);
-	const long long nh = 256LL * ntiles;
-	const long long nscan = nh > n ? nh : n;
-	Sizer z;
-	for (int j = 0; j < 4; j++) z.add<int>(n);
-	z.add<int>(nh); z.add<int>(nh + 1); z.add<int>(scan_part_len(nscan)); z.add<int>(n); z.add<int>((size_t)n + 1);
-	Arena ws{ws_alloc(workspace_alloc, workspace_ctx, z.bytes), 0};
-	if (!ws.p) return GSR_ERR_ALLOC;
-	int* k0 = ws.take<int>(n); int* v0 = ws.take<int>(n); int* k1 = ws.take<int>(n); int* v1 = ws.take<int>(n);
-	int* hist = ws.take<int>(nh); int* offs = ws.take<int>(nh + 1); int* part = ws.take<int>(scan_part_len(nscan));
-	int* head = ws.take<int>(n); int* rank = ws.take<int>((size_t)n + 1);
-	VOX_TRY(hipMemcpyAsync(k0, pair_voxel, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-	VOX_TRY(hipMemcpyAsync(v0, pair_tri_in, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-	const int bits = bits_for(nn);
-	int rc;
-	for (int shift = 0; shift < bits; shift += 8) {
-		hipLaunchKernelGGL(radix_hist<int>, dim3(ntiles), dim3(256), 0, s, k0, n, shift, ntiles, hist);
-		rc = exclusive_scan(hist, (int)nh, offs, part, s);
-		if (rc) return rc;
-		hipLaunchKernelGGL(radix_scatter<int>, dim3(ntiles), dim3(256), 0, s, k0, v0, n, shift, ntiles, offs, k1, v1);
-		int* t = k0; k0 = k1; k1 = t;
-		t = v0; v0 = v1; v1 = t;
-	}
+	int *k0, *v0, *head, *rank;
+	SortBufs<int> sb;   // sb.part serves the scan of the head flags too
+	auto carve = [&](Arena& ws) {
+		k0 = ws.take<int>(n); v0 = ws.take<int>(n); sb = sort_take<int>(ws, n, n);
+		head = ws.take<int>(n); rank = ws.take<int>((size_t)n + 1);
+	};
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemcpyAsync(k0, pair_voxel, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+	GSR_TRY(hipMemcpyAsync(v0, pair_tri_in, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+	int rc = radix_sort(k0, v0, n, bits_for(nn), sb, s);
+	if (rc) return rc;
 	hipLaunchKernelGGL(vox_heads, dim3(blocks(n)), dim3(256), 0, s, k0, n, head);
-	rc = exclusive_scan(head, n, rank, part, s);
+	rc = exclusive_scan(head, n, rank, sb.part, s);
 	if (rc) return rc;
 	hipLaunchKernelGGL(vox_compact, dim3(blocks(n)), dim3(256), 0, s, k0, v0, n, head, rank, n1, n2, voxel_index, pair_start, pair_tri,
 	                   grid_index, occupancy);
-	VOX_TRY(hipMemcpyAsync(num_voxels, rank + n, sizeof(int), hipMemcpyDeviceToHost, s));
-	VOX_TRY(hipStreamSynchronize(s));
+	GSR_TRY(hipMemcpyAsync(num_voxels, rank + n, sizeof(int), hipMemcpyDeviceToHost, s));
+	GSR_TRY(hipStreamSynchronize(s));
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
 

@@ -229,3 +229,19 @@ def test_helper_corner_cases():
             r.interpolate(frb, torch.from_numpy(attr).to(DEV))
     vis = r.visible_faces(fr).cpu().numpy()
     assert np.array_equal(vis, mm.visible_faces(p2f, n))
+
+
+@pytest.mark.parametrize("V", [256, 257])
+def test_vertex_normals_just_past_one_radix_tile(V):
+    """4098 corners (one radix tile and two keys, no multiple of 256) sorted by a vertex id of 8 bits (one pass) and of
+    9 bits (two passes)."""
+    F = 1366
+    assert 3 * F == RADIX_TILE + 2 and (3 * F) % 256 != 0
+    rng = np.random.default_rng(60 + V)
+    v = rng.normal(size=(V, 3)).astype(np.float32)
+    f = rng.integers(0, V, size=(F, 3)).astype(np.int32)
+    f[F // 2, 1], f[-1, 2] = V - 1, V - 1                    # the highest key, in the first tile and as the last corner
+    r = mr().MeshRasterizer(torch.from_numpy(v).to(DEV), torch.from_numpy(f).to(DEV))
+    got = r.vertex_normals().cpu().numpy()
+    want = mm.vertex_normals(v, f)
+    assert np.array_equal(got.view(np.int32), want.view(np.int32)), "normals are not the fixed-order float32 sums"

@@ -207,6 +207,21 @@ def test_general_bounds_and_a_voxel_size_that_is_no_power_of_two():
     assert_same(got32, vox32)
 
 
+# ---------------------------------------------------------------------------------------------- 8b. the pair sort's edges
+@pytest.mark.parametrize("n2", [5, 7])
+def test_pair_sort_past_one_radix_tile_on_one_and_two_digit_grids(n2):
+    """More pairs than one 4096-key radix tile, no multiple of 256, on 7 x 7 x 5 = 245 cells (8 key bits: one pass) and
+    7 x 7 x 7 = 343 cells (9 bits: two passes)."""
+    v, f = mm.soup(seed=31, n=1100)
+    vn = v.astype(np.float64) * 0.3 + np.array([0.44, 0.44, 0.4])
+    vs, lo, hi = 0.125, (0.0, 0.0, 0.0), (0.875, 0.875, 0.125 * n2)
+    assert mm.grid_shape(vs, lo, hi) == (7, 7, n2)
+    got, vox, _ = check(vn, f, vs, lo, hi, closest=False)
+    pairs = got["pair_tri"].shape[0]
+    assert pairs > 4096 and pairs % 256 != 0
+    assert vox["voxel_index"].max() == 7 * 7 * n2 - 1                  # the highest key is there
+
+
 # ---------------------------------------------------------------------------------------------- 9. errors
 def test_errors_leave_the_outputs_untouched():
     from gaustudio_amd import _C, voxelize as vx

@@ -17,6 +17,8 @@ import os
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libgsrast.so")
 _lib = None
@@ -107,7 +109,6 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     An upstream gradient may be ABSENT (None, or the reference's empty tensor): the loss does not use that output, its
     gradient is zero and nothing is read for it (include/gsrast.h gsr_backward); `image_height` / `image_width` are only
     needed when all four are absent (the size is otherwise taken from one that is present)."""
-    import torch
     e = lambda t: torch.Tensor([]) if t is None else t
     dL_dout_color, dL_dout_depth, dL_dout_median_depth, dL_dout_final_opacity = (
         e(dL_dout_color), e(dL_dout_depth), e(dL_dout_median_depth), e(dL_dout_final_opacity))
@@ -133,71 +134,49 @@ def msg_header_words(P):
     return int(L.gsr_msg_header_words(ctypes.c_int(int(P))))
 
 
-def _rc(L, rc):
-    if rc < 0:
-        raise _err(L, rc)
+def _call(name, device, *args):
+    """_abi.call, raising the library's own message (gsr_last_error) on a negative status."""
+    return _abi.call(name, device, *args, fail=_err)
 
 
 def visible_index(radii, msg, counts):
     """Header (K, block bases, mask) of the Gaussians with radii > 0 into the int32 tensor `msg`; counts: int32 scratch [ceil(P/256)]."""
-    L = lib()
-    with torch.cuda.device(radii.device):
-        _rc(L, L.gsr_visible_index(ctypes.c_int(radii.numel()), _ptr(radii), _ptr(msg), _ptr(counts), _stream(radii.device)))
+    _call("gsr_visible_index", radii.device, radii.numel(), radii, msg, counts)
 
 
 def union_index(P, msgs, offsets, out_hdr, counts):
     """Header of the OR of the N = offsets.numel() messages' masks; message r starts at word offsets[r] (int64, device) of the
     int32 tensor msgs."""
-    L = lib()
-    with torch.cuda.device(msgs.device):
-        _rc(L, L.gsr_union_index(ctypes.c_int(int(P)), ctypes.c_int(int(offsets.numel())), _ptr(msgs), _ptr(offsets),
-                                 _ptr(out_hdr), _ptr(counts), _stream(msgs.device)))
+    _call("gsr_union_index", msgs.device, int(P), offsets.numel(), msgs, offsets, out_hdr, counts)
 
 
 def pack_rows(hdr, src, dst, dst_stride, col0=0):
     """dst[row * dst_stride + col0 + c] = src[g, c] for the header's Gaussians g (src float32 [P, C], dst float32 flat)."""
-    L = lib()
     P, C = src.shape[0], src.numel() // max(src.shape[0], 1)
-    with torch.cuda.device(src.device):
-        _rc(L, L.gsr_pack_rows(ctypes.c_int(P), ctypes.c_int(C), _ptr(hdr), _ptr(src), _ptr(dst), ctypes.c_int(int(dst_stride)),
-                               ctypes.c_int(int(col0)), _stream(src.device)))
+    _call("gsr_pack_rows", src.device, P, C, hdr, src, dst, int(dst_stride), int(col0))
 
 
 def unpack_rows(hdr, src, src_stride, col0, dst):
     """dst[g, c] = src[row * src_stride + col0 + c] for the header's Gaussians g; the other rows of dst stay as they are."""
-    L = lib()
     P, C = dst.shape[0], dst.numel() // max(dst.shape[0], 1)
-    with torch.cuda.device(dst.device):
-        _rc(L, L.gsr_unpack_rows(ctypes.c_int(P), ctypes.c_int(C), _ptr(hdr), _ptr(src), ctypes.c_int(int(src_stride)),
-                                 ctypes.c_int(int(col0)), _ptr(dst), _stream(dst.device)))
+    _call("gsr_unpack_rows", dst.device, P, C, hdr, src, int(src_stride), int(col0), dst)
 
 
 def pack_geometry(hdr, g_means3D, g_opacity, g_scales, g_rotations, rows, flag):
     """rows[r, 0:11] = [means3D 3 | opacity 1 | scales 3 | rotations 4] gradients of the r-th Gaussian of the header; flag (int32[1],
     cleared by the caller) |= 1 when a Gaussian outside the header has a non-zero value."""
-    L = lib()
-    P = g_means3D.shape[0]
-    with torch.cuda.device(rows.device):
-        _rc(L, L.gsr_pack_geometry(ctypes.c_int(P), _ptr(hdr), _ptr(g_means3D), _ptr(g_opacity), _ptr(g_scales), _ptr(g_rotations),
-                                   _ptr(rows), _ptr(flag), _stream(rows.device)))
+    _call("gsr_pack_geometry", rows.device, g_means3D.shape[0], hdr, g_means3D, g_opacity, g_scales, g_rotations, rows, flag)
 
 
 def unpack_geometry(hdr, rows, g_means3D, g_opacity, g_scales, g_rotations):
-    L = lib()
-    P = g_means3D.shape[0]
-    with torch.cuda.device(rows.device):
-        _rc(L, L.gsr_unpack_geometry(ctypes.c_int(P), _ptr(hdr), _ptr(rows), _ptr(g_means3D), _ptr(g_opacity), _ptr(g_scales),
-                                     _ptr(g_rotations), _stream(rows.device)))
+    _call("gsr_unpack_geometry", rows.device, g_means3D.shape[0], hdr, rows, g_means3D, g_opacity, g_scales, g_rotations)
 
 
 def sh_grad_from_packed(means3D, campos, msgs, offsets, degree, out):
     """sh_grad_from_colors reading N = offsets.numel() packed messages (header + rows of 3 floats, message r at word offsets[r] of the
     int32 tensor msgs) instead of dense colours."""
-    L = lib()
-    P, M = out.shape[0], out.shape[1]
-    with torch.cuda.device(out.device):
-        _rc(L, L.gsr_sh_grad_from_packed(ctypes.c_int(P), ctypes.c_int(int(degree)), ctypes.c_int(M), ctypes.c_int(int(offsets.numel())),
-                                         _ptr(means3D), _ptr(campos), _ptr(msgs), _ptr(offsets), _ptr(out), _stream(out.device)))
+    _call("gsr_sh_grad_from_packed", out.device, out.shape[0], int(degree), out.shape[1], offsets.numel(), means3D, campos, msgs,
+          offsets, out)
     return out
 
 
@@ -222,16 +201,10 @@ def set_grad_arena(outs, keys=(), sh_chunks=1, hook=None, colors_out=None, band_
 def band_classes(radii, geom_buffer, split_tile_row):
     """(first[P], second[P]) int32: the two Gaussian classes of a banded backward cut at tile row `split_tile_row`
     (include/gsrast.h gsr_band_classes)."""
-    import torch
-    L = lib()
     P = int(radii.shape[0])
     first = torch.empty(P, dtype=torch.int32, device=radii.device)
     second = torch.empty(P, dtype=torch.int32, device=radii.device)
-    with torch.cuda.device(radii.device):
-        rc = L.gsr_band_classes(ctypes.c_int(P), _ptr(radii), _ptr(geom_buffer), ctypes.c_int(int(split_tile_row)), _ptr(first), _ptr(second),
-                                _stream(radii.device))
-    if rc < 0:
-        raise _err(L, rc)
+    _call("gsr_band_classes", radii.device, P, radii, geom_buffer, int(split_tile_row), first, second)
     return first, second
 
 
@@ -251,34 +224,22 @@ def get_option(name):
 
 def selftest(device=None):
     """Bit mask of the device arithmetic identities composite_bwd relies on (3 = all hold)."""
-    L = lib()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    with torch.cuda.device(dev):
-        rc = L.gsr_selftest(_stream(dev))
-    if rc < 0:
-        raise _err(L, rc)
-    return rc
+    return _call("gsr_selftest", dev)
 
 
 def inspect_counts(imgBuffer, width, height):
     """{'num_binned': instances actually binned (length of point_list), 'max_tile': longest tile list,
     'num_rendered': the reference-defined count rasterize_gaussians returned}."""
-    L = lib()
-    dev = imgBuffer.device
     out = (ctypes.c_uint32 * 4)()
-    with torch.cuda.device(dev):
-        rc = L.gsr_inspect_counts(_ptr(imgBuffer), ctypes.c_int(width), ctypes.c_int(height), out, _stream(dev))
-    if rc < 0:
-        raise _err(L, rc)
+    _call("gsr_inspect_counts", imgBuffer.device, imgBuffer, width, height, out)
     return dict(num_binned=int(out[0]), max_tile=int(out[1]), num_rendered=int(out[2]), overflow=int(out[3]))
 
 
 def inspect_staged(imgBuffer, width, height):
     """Instances composite_fwd actually staged for the frame (it stops fetching a tile's list once every pixel has saturated)."""
-    import ctypes
-    L = lib()
     out = ctypes.c_ulonglong(0)
-    _rc(L, L.gsr_inspect_staged(_ptr(imgBuffer), ctypes.c_int(int(width)), ctypes.c_int(int(height)), ctypes.byref(out), _stream(imgBuffer.device)))
+    _call("gsr_inspect_staged", imgBuffer.device, imgBuffer, int(width), int(height), ctypes.byref(out))
     return int(out.value)
 
 
@@ -290,7 +251,6 @@ def mark_visible(means3D, viewmatrix, projmatrix):
 # ---- introspection of the opaque buffers (tests / debugging; include/gsrast.h gsr_inspect_*) ----
 
 def inspect_geometry(geomBuffer, radii):
-    L = lib()
     dev = radii.device
     P = radii.numel()
     out = dict(means2D=torch.empty((P, 2), dtype=torch.float32, device=dev),
@@ -299,39 +259,24 @@ def inspect_geometry(geomBuffer, radii):
                rgb=torch.empty((P, 3), dtype=torch.float32, device=dev),
                clamped=torch.empty((P, 3), dtype=torch.uint8, device=dev),
                tiles_touched=torch.empty((P,), dtype=torch.int32, device=dev))
-    with torch.cuda.device(dev):
-        rc = L.gsr_inspect_geometry(_ptr(geomBuffer), ctypes.c_int(P), _ptr(radii), _ptr(out["means2D"]),
-                                    _ptr(out["depths"]), _ptr(out["conic_opacity"]), _ptr(out["rgb"]),
-                                    _ptr(out["clamped"]), _ptr(out["tiles_touched"]), _stream(dev))
-    if rc < 0:
-        raise _err(L, rc)
+    _call("gsr_inspect_geometry", dev, geomBuffer, P, radii, *out.values())
     return out
 
 
 def inspect_binning(binningBuffer, imgBuffer, R, width, height):
-    L = lib()
     dev = imgBuffer.device
     T = ((width + 15) // 16) * ((height + 15) // 16)
     point_list = torch.empty((max(int(R), 0),), dtype=torch.int32, device=dev)
     ranges = torch.empty((T, 2), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.gsr_inspect_binning(_ptr(binningBuffer), _ptr(imgBuffer), ctypes.c_int(int(R)), ctypes.c_int(width),
-                                   ctypes.c_int(height), _ptr(point_list), _ptr(ranges), _stream(dev))
-    if rc < 0:
-        raise _err(L, rc)
+    _call("gsr_inspect_binning", dev, binningBuffer, imgBuffer, int(R), width, height, point_list, ranges)
     return point_list, ranges
 
 
 def inspect_image(imgBuffer, width, height):
-    L = lib()
     dev = imgBuffer.device
     final_T = torch.empty((height, width), dtype=torch.float32, device=dev)
     n_contrib = torch.empty((height, width), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.gsr_inspect_image(_ptr(imgBuffer), ctypes.c_int(width), ctypes.c_int(height), _ptr(final_T),
-                                 _ptr(n_contrib), _stream(dev))
-    if rc < 0:
-        raise _err(L, rc)
+    _call("gsr_inspect_image", dev, imgBuffer, width, height, final_T, n_contrib)
     return final_T, n_contrib
 
 

@@ -13,51 +13,26 @@ import ctypes
 
 import torch
 
-from . import _C
-from .mesh_raster import _Workspace, _on_rocm
+from ._abi import call, check_mesh, on_rocm, same_device
 
 last_rounds = 0
 """Hook-and-jump rounds of the most recent cluster_connected_triangles call (O(log F), not the mesh's diameter)."""
 
-
-def _check(name, rc):
-    if rc == -2:
-        raise ValueError(f"{name}: invalid argument (a face index out of range or a bad size)")
-    if rc < 0:
-        raise RuntimeError(f"{name} failed (rc={rc})")
-    return rc
+_ERRORS = {-2: "{what}: invalid argument (a face index out of range or a bad size)"}
 
 
-def _faces(faces):
-    if not torch.is_tensor(faces):
-        raise TypeError("faces must be a torch tensor")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces must have shape [F, 3], got {list(faces.shape)}")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"faces must be int32 or int64, got {faces.dtype}")
-    if faces.shape[0] >= 2 ** 31 // 3:
-        raise ValueError("meshes are limited to F < 2^31 / 3 faces")
-    _on_rocm(faces=faces)
-    if faces.dtype == torch.int64 and faces.numel():
-        lo, hi = int(faces.min()), int(faces.max())
-        if lo < -2 ** 31 or hi >= 2 ** 31:
-            raise ValueError("face indices out of range")
-    return faces.to(torch.int32).contiguous()
-
-
-def _vertices(vertices, device):
-    if not torch.is_tensor(vertices):
-        raise TypeError("vertices must be a torch tensor")
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must have shape [V, 3], got {list(vertices.shape)}")
+def _mesh(vertices, faces):
+    """(vertices float32 or None, faces int32), contiguous, checked to be one mesh on one ROCm device."""
+    check_mesh(vertices, faces, vertex_dtypes=None, max_verts=(2 ** 31, "meshes are limited to V < 2^31 vertices"),
+               max_faces=(2 ** 31 // 3, "meshes are limited to F < 2^31 / 3 faces"), device_exc=RuntimeError)
+    f = faces.to(torch.int32).contiguous()
+    if vertices is None:
+        return None, f
     if not vertices.dtype.is_floating_point:
         raise TypeError(f"vertices must be a floating-point tensor, got {vertices.dtype}")
-    if vertices.shape[0] >= 2 ** 31:
-        raise ValueError("meshes are limited to V < 2^31 vertices")
-    _on_rocm(vertices=vertices)
-    if vertices.device != device:
-        raise ValueError(f"vertices are on {vertices.device}, faces on {device}")
-    return vertices.to(torch.float32).contiguous()
+    if vertices.device != f.device:
+        raise ValueError(f"vertices are on {vertices.device}, faces on {f.device}")
+    return vertices.to(torch.float32).contiguous(), f
 
 
 def cluster_connected_triangles(faces, num_verts=None, vertices=None):
@@ -65,9 +40,8 @@ def cluster_connected_triangles(faces, num_verts=None, vertices=None):
     cluster_area [C] float64 or None).  Triangles that share an undirected edge are connected; clusters are numbered by their
     lowest triangle index.  The area needs `vertices` [V,3]; without them pass `num_verts` (default: the largest index + 1)."""
     global last_rounds
-    f = _faces(faces)
+    v, f = _mesh(vertices, faces)
     dev = f.device
-    v = _vertices(vertices, dev) if vertices is not None else None
     F = f.shape[0]
     if num_verts is None:
         num_verts = v.shape[0] if v is not None else (int(f.max()) + 1 if F else 0)
@@ -81,21 +55,14 @@ def cluster_connected_triangles(faces, num_verts=None, vertices=None):
     clusters = torch.empty(F, dtype=torch.int32, device=dev)
     counts = torch.empty(F, dtype=torch.int32, device=dev)
     rounds = ctypes.c_int(0)
-    ws = _Workspace(dev)
-    L = _C.lib()
     with torch.cuda.device(dev):
-        rc = L.gsr_mesh_cluster_triangles(ws.fn, None, _C._ptr(f), ctypes.c_int(F), ctypes.c_int(V), _C._ptr(clusters),
-                                          _C._ptr(counts), ctypes.byref(rounds), _C._stream(dev))
-        C = _check("gsr_mesh_cluster_triangles", rc)
+        C = call("gsr_mesh_cluster_triangles", dev, f, F, V, clusters, counts, ctypes.byref(rounds), workspace=True, errors=_ERRORS)
         last_rounds = int(rounds.value)
         counts = counts[:C].clone()
         area = None
         if v is not None:
             area = torch.empty(C, dtype=torch.float64, device=dev)
-            ws2 = _Workspace(dev)
-            rc = L.gsr_mesh_cluster_area(ws2.fn, None, _C._ptr(v), ctypes.c_int(V), _C._ptr(f), ctypes.c_int(F), _C._ptr(clusters),
-                                         ctypes.c_int(C), _C._ptr(area), _C._stream(dev))
-            _check("gsr_mesh_cluster_area", rc)
+            call("gsr_mesh_cluster_area", dev, v, V, f, F, clusters, C, area, workspace=True, errors=_ERRORS)
     return clusters, counts, area
 
 
@@ -105,9 +72,8 @@ def remove_triangles_by_mask(vertices, faces, remove_mask):
     order; the index maps (new -> old) carry per-vertex or per-face attributes across: colours[vertex_index.long()]."""
     if not torch.is_tensor(vertices) or not torch.is_tensor(faces):
         raise TypeError("vertices and faces must be torch tensors")
-    f = _faces(faces)
+    v, f = _mesh(vertices, faces)
     dev = f.device
-    v = _vertices(vertices, dev)
     F, V = f.shape[0], v.shape[0]
     if not torch.is_tensor(remove_mask):
         raise TypeError("remove_mask must be a torch tensor")
@@ -115,9 +81,8 @@ def remove_triangles_by_mask(vertices, faces, remove_mask):
         raise ValueError(f"remove_mask must have shape [{F}], got {list(remove_mask.shape)}")
     if remove_mask.dtype not in (torch.bool, torch.uint8):
         raise TypeError(f"remove_mask must be bool or uint8, got {remove_mask.dtype}")
-    _on_rocm(remove_mask=remove_mask)
-    if remove_mask.device != dev:
-        raise ValueError(f"remove_mask is on {remove_mask.device}, the mesh on {dev}")
+    on_rocm(remove_mask=remove_mask)
+    same_device(dev, remove_mask=remove_mask)
     i32 = dict(dtype=torch.int32, device=dev)
     if F == 0:
         return torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), **i32), torch.zeros(0, **i32), torch.zeros(0, **i32)
@@ -127,12 +92,7 @@ def remove_triangles_by_mask(vertices, faces, remove_mask):
     vidx = torch.empty(V, **i32)
     fidx = torch.empty(F, **i32)
     nv = ctypes.c_int(0)
-    ws = _Workspace(dev)
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_mesh_compact(ws.fn, None, _C._ptr(v), ctypes.c_int(V), _C._ptr(f), ctypes.c_int(F), _C._ptr(keep),
-                                       _C._ptr(out_v), _C._ptr(out_f), _C._ptr(vidx), _C._ptr(fidx), ctypes.byref(nv),
-                                       _C._stream(dev))
-    nf = _check("gsr_mesh_compact", rc)
+    nf = call("gsr_mesh_compact", dev, v, V, f, F, keep, out_v, out_f, vidx, fidx, ctypes.byref(nv), workspace=True, errors=_ERRORS)
     nv = int(nv.value)
     return out_v[:nv].clone(), out_f[:nf].clone(), vidx[:nv].clone(), fidx[:nf].clone()
 
@@ -149,8 +109,7 @@ def remove_small_components(vertices, faces, ratio_threshold=0.5, return_index=F
     Returns (vertices', faces', number of removed triangles), with return_index also (vertex_index, face_index)."""
     if not torch.is_tensor(vertices) or not torch.is_tensor(faces):
         raise TypeError("vertices and faces must be torch tensors")
-    f = _faces(faces)
-    v = _vertices(vertices, f.device)
+    v, f = _mesh(vertices, faces)
     if f.shape[0] == 0:
         i32 = dict(dtype=torch.int32, device=f.device)
         out = (torch.zeros((0, 3), dtype=torch.float32, device=f.device), torch.zeros((0, 3), **i32), 0)

@@ -8,13 +8,11 @@ Gaussian f * n + k is the k-th of face f.  Contract and the reference's quirks (
 whose raw value is log(1e-7), the sign() cases of normal2rotation, the quaternion that is not normalised, torch.cross along the
 last axis): INTEGRATION.md s21.  vertex_colors typically come from texture_bake.  ROCm tensors only, no CPU fallback.
 """
-import ctypes
-
 import torch
 
-from . import _C
+from ._abi import call, on_rocm, same_device
 from .formats import GaussianCloud
-from .mesh_raster import MeshRasterizer, _Workspace
+from .mesh_raster import MeshRasterizer
 from .voxelize import _mesh
 
 N_PER_TRIANGLE = (1, 3, 4, 6)
@@ -46,11 +44,8 @@ def mesh_seeds(vertices, faces, vertex_colors=None, vertex_normals=None, n_per_t
         if torch.is_tensor(vertices) and tuple(vertex_normals.shape) != tuple(vertices.shape):
             raise ValueError(f"vertex_normals must have shape {list(vertices.shape)} like vertices, got {list(vertex_normals.shape)}")
     dev = _mesh(vertices, faces, vertex_colors, vertex_dtypes=(torch.float32,))
-    if vertex_normals is not None:
-        if vertex_normals.device.type != "cuda":
-            raise ValueError(f"vertex_normals is on '{vertex_normals.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
-        if vertex_normals.device != dev:
-            raise ValueError(f"vertex_normals is on {vertex_normals.device}, vertices on {dev}")
+    on_rocm(ValueError, vertex_normals=vertex_normals)
+    same_device(dev, ref="vertices", vertex_normals=vertex_normals)
     n = int(n_per_triangle)
     v = vertices.detach().contiguous()
     f = faces.detach().to(torch.int32).contiguous()
@@ -69,14 +64,8 @@ def mesh_seeds(vertices, faces, vertex_colors=None, vertex_normals=None, n_per_t
         nrm = vertex_normals.detach().contiguous()
     new = lambda c: torch.empty((P, c), dtype=torch.float32, device=dev)
     xyz, f_dc, scale, rot = new(3), new(3), new(3), new(4)
-    ws = _Workspace(dev)
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_mesh_seeds(ws.fn, None, _C._ptr(v), _C._ptr(nrm), _C._ptr(col), ctypes.c_int(V), _C._ptr(f), ctypes.c_int(F),
-                                     ctypes.c_int(n), _C._ptr(xyz), _C._ptr(f_dc), _C._ptr(scale), _C._ptr(rot), _C._stream(dev))
-    if rc == -2:
-        raise ValueError("mesh_seeds: a face index lies outside [0, V)")
-    if rc < 0:
-        raise RuntimeError(f"gsr_mesh_seeds failed (rc={rc})")
+    call("gsr_mesh_seeds", dev, v, nrm, col, V, f, F, n, xyz, f_dc, scale, rot, workspace=True,
+         errors={-2: "mesh_seeds: a face index lies outside [0, V)"})
     return GaussianCloud(xyz=xyz, f_dc=f_dc.reshape(P, 1, 3),
                          f_rest=torch.zeros((P, (int(sh_degree) + 1) ** 2 - 1, 3), dtype=torch.float32, device=dev),
                          opacity=torch.full((P, 1), float("inf"), dtype=torch.float32, device=dev), scale=scale, rot=rot)

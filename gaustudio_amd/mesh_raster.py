@@ -17,30 +17,13 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _C
+from ._abi import call, check_mesh, on_rocm
 
 MAX_CHANNELS = 4
 
 Fragments = namedtuple("Fragments", ["pix_to_face", "zbuf", "bary_coords"])
 Fragments.__doc__ = """pix_to_face [H,W] int32, zbuf [H,W] float32 (camera-space z), bary_coords [H,W,3] float32; -1 on background.
 (PyTorch3D's Fragments hold the same values with a batch and a faces_per_pixel axis of 1.)"""
-
-_ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
-
-
-class _Workspace:
-    """gsr_alloc_fn for the duration of one call: torch uint8 tensors (stream-ordered through torch's caching allocator),
-    kept alive until the call has been enqueued."""
-
-    def __init__(self, device):
-        self.device = device
-        self.bufs = []
-        self.fn = _ALLOC_FN(self._alloc)
-
-    def _alloc(self, ctx, nbytes):
-        t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
-        self.bufs.append(t)
-        return t.data_ptr()
 
 
 def _host_f32(name, m, shape):
@@ -51,18 +34,8 @@ def _host_f32(name, m, shape):
     return (ctypes.c_float * a.size)(*a.ravel().tolist())
 
 
-def _on_rocm(**tensors):
-    for name, t in tensors.items():
-        if t.device.type != "cuda":
-            raise RuntimeError(f"{name} is on '{t.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
-
-
-def _check(name, rc):
-    if rc == -2:
-        raise ValueError(f"{name}: invalid argument (a face index out of range, a bad size or singular intrinsics)")
-    if rc < 0:
-        raise RuntimeError(f"{name} failed (rc={rc})")
-    return rc
+_ERRORS = {-2: "{what}: invalid argument (a face index out of range, a bad size or singular intrinsics)"}
+_LIMIT = "meshes are limited to V < 2^31 vertices and F < 2^31 / 3 faces"
 
 
 class MeshRasterizer:
@@ -71,19 +44,8 @@ class MeshRasterizer:
     def __init__(self, vertices, faces):
         if not torch.is_tensor(vertices) or not torch.is_tensor(faces):
             raise TypeError("vertices and faces must be torch tensors")
-        if vertices.dim() != 2 or vertices.shape[1] != 3:
-            raise ValueError(f"vertices must have shape [V, 3], got {list(vertices.shape)}")
-        if faces.dim() != 2 or faces.shape[1] != 3:
-            raise ValueError(f"faces must have shape [F, 3], got {list(faces.shape)}")
-        if faces.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"faces must be int32 or int64, got {faces.dtype}")
-        if vertices.shape[0] >= 2 ** 31 or faces.shape[0] >= 2 ** 31 // 3:
-            raise ValueError("meshes are limited to V < 2^31 vertices and F < 2^31 / 3 faces")
-        _on_rocm(vertices=vertices, faces=faces)
-        if faces.dtype == torch.int64 and faces.numel():
-            lo, hi = int(faces.min()), int(faces.max())
-            if lo < -2 ** 31 or hi >= 2 ** 31:
-                raise ValueError("face indices out of range")
+        check_mesh(vertices, faces, vertex_dtypes=None, max_verts=(2 ** 31, _LIMIT), max_faces=(2 ** 31 // 3, _LIMIT),
+                   device_exc=RuntimeError)
         self.device = vertices.device
         self.verts = vertices.to(torch.float32).contiguous()
         self.faces = faces.to(device=self.device, dtype=torch.int32).contiguous()
@@ -109,13 +71,8 @@ class MeshRasterizer:
         p2f = torch.empty((H, W), dtype=torch.int32, device=dev)
         zbuf = torch.empty((H, W), dtype=torch.float32, device=dev)
         bary = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-        ws = _Workspace(dev)
-        with torch.cuda.device(dev):
-            rc = _C.lib().gsr_mesh_rasterize(ws.fn, None, _C._ptr(self.verts), ctypes.c_int(self.num_verts), _C._ptr(self.faces),
-                                             ctypes.c_int(self.num_faces), K, E, ctypes.c_int(H), ctypes.c_int(W),
-                                             ctypes.c_int(int(bool(cull_backfaces))), ctypes.c_float(float(z_near)),
-                                             _C._ptr(p2f), _C._ptr(zbuf), _C._ptr(bary), _C._stream(dev))
-        self.last_binned = _check("gsr_mesh_rasterize", rc)
+        self.last_binned = call("gsr_mesh_rasterize", dev, self.verts, self.num_verts, self.faces, self.num_faces, K, E, H, W,
+                                bool(cull_backfaces), ctypes.c_float(float(z_near)), p2f, zbuf, bary, workspace=True, errors=_ERRORS)
         return Fragments(p2f, zbuf, bary)
 
     def _fragments(self, fragments, need_bary):
@@ -125,7 +82,7 @@ class MeshRasterizer:
             raise TypeError("fragments.pix_to_face must be an int32 tensor (MeshRasterizer.rasterize output)")
         if need_bary and (not torch.is_tensor(bary) or bary.dtype != torch.float32 or bary.shape != (*p2f.shape, 3)):
             raise TypeError(f"fragments.bary_coords must be a float32 tensor of shape {[*p2f.shape, 3]}")
-        _on_rocm(pix_to_face=p2f, **({"bary_coords": bary} if need_bary else {}))
+        on_rocm(pix_to_face=p2f, **({"bary_coords": bary} if need_bary else {}))
         for t in (p2f, bary) if need_bary else (p2f,):
             if t.device != self.device:
                 raise ValueError(f"fragments are on {t.device}, the mesh on {self.device}")
@@ -138,28 +95,20 @@ class MeshRasterizer:
         C = attr.shape[1]
         if not 1 <= C <= MAX_CHANNELS:
             raise ValueError(f"attr must have 1..{MAX_CHANNELS} channels, got {C}")
-        _on_rocm(attr=attr)
+        on_rocm(attr=attr)
         a = attr.to(device=self.device, dtype=torch.float32).contiguous()
         p2f, bary = self._fragments(fragments, need_bary=True)
         out = torch.empty((*p2f.shape, C), dtype=torch.float32, device=self.device)
-        ws = _Workspace(self.device)
-        with torch.cuda.device(self.device):
-            rc = _C.lib().gsr_mesh_interpolate(ws.fn, None, _C._ptr(self.faces), ctypes.c_int(self.num_faces), _C._ptr(p2f),
-                                               _C._ptr(bary), ctypes.c_int(p2f.numel()), _C._ptr(a), ctypes.c_int(self.num_verts),
-                                               ctypes.c_int(C), _C._ptr(out), _C._stream(self.device))
-        _check("gsr_mesh_interpolate", rc)
+        call("gsr_mesh_interpolate", self.device, self.faces, self.num_faces, p2f, bary, p2f.numel(), a, self.num_verts, C, out,
+             workspace=True, errors=_ERRORS)
         return out
 
     def vertex_normals(self):
         """Meshes.verts_normals_packed: [V,3] float32, summed in a fixed order (cached)."""
         if self._normals is None:
             n = torch.empty((self.num_verts, 3), dtype=torch.float32, device=self.device)
-            ws = _Workspace(self.device)
-            with torch.cuda.device(self.device):
-                rc = _C.lib().gsr_mesh_vertex_normals(ws.fn, None, _C._ptr(self.verts), ctypes.c_int(self.num_verts),
-                                                      _C._ptr(self.faces), ctypes.c_int(self.num_faces), _C._ptr(n),
-                                                      _C._stream(self.device))
-            _check("gsr_mesh_vertex_normals", rc)
+            call("gsr_mesh_vertex_normals", self.device, self.verts, self.num_verts, self.faces, self.num_faces, n,
+                 workspace=True, errors=_ERRORS)
             self._normals = n
         return self._normals
 
@@ -182,11 +131,7 @@ class MeshRasterizer:
         mask.nonzero() gives its sorted list)."""
         p2f, _ = self._fragments(fragments, need_bary=False)
         vis = torch.empty(self.num_faces, dtype=torch.uint8, device=self.device)
-        ws = _Workspace(self.device)
-        with torch.cuda.device(self.device):
-            rc = _C.lib().gsr_mesh_visible_faces(ws.fn, None, _C._ptr(p2f), ctypes.c_int(p2f.numel()), ctypes.c_int(self.num_faces),
-                                                 _C._ptr(vis), _C._stream(self.device))
-        _check("gsr_mesh_visible_faces", rc)
+        call("gsr_mesh_visible_faces", self.device, p2f, p2f.numel(), self.num_faces, vis, workspace=True, errors=_ERRORS)
         return vis.bool()
 
 

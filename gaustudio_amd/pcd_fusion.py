@@ -16,26 +16,9 @@ import math
 
 import torch
 
-from . import _C
+from ._abi import call, on_rocm
 
 MAX_K = 64
-
-_ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
-
-
-class _Workspace:
-    """gsr_alloc_fn for the duration of one call: hands out torch uint8 tensors (stream-ordered through torch's caching
-    allocator) and keeps them alive until the call has been enqueued."""
-
-    def __init__(self, device):
-        self.device = device
-        self.bufs = []
-        self.fn = _ALLOC_FN(self._alloc)
-
-    def _alloc(self, ctx, nbytes):
-        t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
-        self.bufs.append(t)
-        return t.data_ptr()
 
 
 def _device_tensor(name, t, shape_last=None, dtypes=(torch.float32,)):
@@ -46,13 +29,6 @@ def _device_tensor(name, t, shape_last=None, dtypes=(torch.float32,)):
     if t.dtype not in dtypes:
         raise TypeError(f"{name} must be one of {[str(d) for d in dtypes]}, got {t.dtype}")
     return t
-
-
-def _on_rocm(**tensors):
-    """Checked after the shapes, dtypes and k, so that those errors need no device."""
-    for name, t in tensors.items():
-        if t is not None and t.device.type != "cuda":
-            raise RuntimeError(f"{name} is on '{t.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
 
 
 def _check_k(k, n, what="k"):
@@ -68,17 +44,8 @@ def _points(name, p):
     return _device_tensor(name, p, 3, (torch.float32, torch.float64))
 
 
-_ERR_NONFINITE, _ERR_NONFINITE_QUERY = -5, -6   # GSR_ERR_NONFINITE, GSR_ERR_NONFINITE_QUERY (include/gsrast.h)
-
-
-def _rc(name, rc):
-    if rc == _ERR_NONFINITE:
-        raise ValueError(f"{name}: a point coordinate is not finite")
-    if rc == _ERR_NONFINITE_QUERY:
-        raise ValueError(f"{name}: a coordinate of the queries is not finite")
-    if rc < 0:
-        raise RuntimeError(f"{name} failed (rc={rc})")
-    return rc
+# GSR_ERR_NONFINITE, GSR_ERR_NONFINITE_QUERY (include/gsrast.h)
+_ERRORS = {-5: "{what}: a point coordinate is not finite", -6: "{what}: a coordinate of the queries is not finite"}
 
 
 # ------------------------------------------------------------------------------------------------------------- kNN
@@ -91,7 +58,7 @@ def knn(points, k, queries=None):
     pts = _points("points", points)
     q = None if queries is None else _points("queries", queries)
     _check_k(k, pts.shape[0])
-    _on_rocm(points=pts, queries=q)
+    on_rocm(points=pts, queries=q)
     pts = pts.to(torch.float32).contiguous()
     if q is not None:
         if q.device != pts.device:
@@ -100,14 +67,10 @@ def knn(points, k, queries=None):
     nq = pts.shape[0] if q is None else q.shape[0]
     dist2 = torch.empty((nq, k), dtype=torch.float64, device=pts.device)
     idx = torch.empty((nq, k), dtype=torch.int64, device=pts.device)
-    ws = _Workspace(pts.device)
     # an empty `queries` has no address to pass (a NULL pointer means "the points themselves"): the points' address
     # stands in for it, and with num_queries = 0 nothing is read through it
-    qptr = _C._ptr(pts) if q is not None and nq == 0 else _C._ptr(q)
-    with torch.cuda.device(pts.device):
-        rc = _C.lib().gsr_knn(ws.fn, None, _C._ptr(pts), ctypes.c_int(pts.shape[0]), qptr, ctypes.c_int(nq),
-                              ctypes.c_int(k), _C._ptr(dist2), _C._ptr(idx), _C._stream(pts.device))
-    _rc("knn", rc)
+    call("gsr_knn", pts.device, pts, pts.shape[0], pts if q is not None and nq == 0 else q, nq, k, dist2, idx,
+         workspace=True, what="knn", errors=_ERRORS)
     return dist2, idx
 
 
@@ -135,7 +98,7 @@ def view_records(median_map, final_opacity, world_normals, scene_radius):
     wn = _device_tensor("world_normals", world_normals)
     if wn.shape != (H, W, 3):
         raise ValueError(f"world_normals must have shape [{H}, {W}, 3]")
-    _on_rocm(median_map=median_map, final_opacity=op, world_normals=wn)
+    on_rocm(median_map=median_map, final_opacity=op, world_normals=wn)
     valid = (median_map[0] < scene_radius * 0.8) & (op > 0.5)
     valid = (wn.sum(dim=-1) > -3) & valid
     return median_map[2].int()[valid], (-wn[valid]).contiguous(), op[valid].contiguous()
@@ -150,7 +113,7 @@ class NormalFusion:
 
     def __init__(self, xyz):
         xyz = _device_tensor("xyz", xyz, 3)
-        _on_rocm(xyz=xyz)
+        on_rocm(xyz=xyz)
         self.xyz = xyz.contiguous()
         self.device = xyz.device
         self.num_records = 0
@@ -166,7 +129,7 @@ class NormalFusion:
         n = ids.shape[0]
         if normals.shape[0] != n or conf.shape[0] != n:
             raise ValueError("ids, normals and confidences must have the same length")
-        _on_rocm(ids=ids, normals=normals, confidences=conf)
+        on_rocm(ids=ids, normals=normals, confidences=conf)
         if ids.device != self.device or normals.device != self.device or conf.device != self.device:
             raise ValueError("records must be on the device of xyz")
         t = torch.as_tensor(w2c_translation, dtype=torch.float32).detach().cpu().reshape(-1)
@@ -185,11 +148,8 @@ class NormalFusion:
         normals = normals.contiguous()
         conf = conf.contiguous()
         tc = (ctypes.c_float * 3)(*[float(v) for v in t.tolist()])
-        with torch.cuda.device(self.device):
-            rc = _C.lib().gsr_fusion_records(_C._ptr(self.xyz), ctypes.c_int(self.xyz.shape[0]), _C._ptr(ids), _C._ptr(normals),
-                                             _C._ptr(conf), ctypes.c_int(n), tc, _C._ptr(self.records[self.num_records:]),
-                                             _C._ptr(self.status), _C._stream(self.device))
-        _rc("gsr_fusion_records", rc)
+        call("gsr_fusion_records", self.device, self.xyz, self.xyz.shape[0], ids, normals, conf, n, tc,
+             self.records[self.num_records:], self.status, errors=_ERRORS)
         self.num_records = need
 
     def finalize(self, k=10, sigma=0.1, consistency=0.8):
@@ -203,21 +163,15 @@ class NormalFusion:
         cap = max(min(n, self.xyz.shape[0]), 1)
         uids = torch.empty(cap, dtype=torch.int32, device=self.device)
         mean = torch.empty((cap, 3), dtype=torch.float32, device=self.device)
-        L = _C.lib()
         with torch.cuda.device(self.device):
-            st = _C._stream(self.device)
-            ws = _Workspace(self.device)
-            U = _rc("gsr_fusion_group", L.gsr_fusion_group(ws.fn, None, _C._ptr(self.records), ctypes.c_int(n),
-                                                           ctypes.c_int(self.xyz.shape[0]), ctypes.c_float(consistency),
-                                                           _C._ptr(uids), _C._ptr(mean), st))
+            U = call("gsr_fusion_group", self.device, self.records, n, self.xyz.shape[0], ctypes.c_float(consistency), uids, mean,
+                     workspace=True, errors=_ERRORS)
             if U < k:
                 raise ValueError(f"normal fusion needs at least k = {k} fused points for the smoothing, got {U}")
             uids, mean = uids[:U], mean[:U]
             out = torch.empty((U, 3), dtype=torch.float32, device=self.device)
-            ws2 = _Workspace(self.device)
-            _rc("gsr_fusion_smooth", L.gsr_fusion_smooth(ws2.fn, None, _C._ptr(self.xyz), _C._ptr(uids), _C._ptr(mean),
-                                                         ctypes.c_int(U), ctypes.c_int(k), ctypes.c_float(sigma),
-                                                         _C._ptr(out), st))
+            call("gsr_fusion_smooth", self.device, self.xyz, uids, mean, U, k, ctypes.c_float(sigma), out, workspace=True,
+                 errors=_ERRORS)
         return uids, out
 
 
@@ -238,17 +192,13 @@ def statistical_outlier_mask(points, nb_neighbors=50, std_ratio=2.0, return_dist
     n = pts.shape[0]
     if not isinstance(nb_neighbors, int) or nb_neighbors < 1 or nb_neighbors > MAX_K:
         raise ValueError(f"nb_neighbors must be in [1, {MAX_K}], got {nb_neighbors}")
-    _on_rocm(points=pts)
+    on_rocm(points=pts)
     pts = pts.to(torch.float32).contiguous()
     keep = torch.zeros(n, dtype=torch.uint8, device=pts.device)
     dist = torch.empty(n, dtype=torch.float64, device=pts.device) if return_distances else None
     if n:
-        ws = _Workspace(pts.device)
-        with torch.cuda.device(pts.device):
-            rc = _C.lib().gsr_outlier_statistical(ws.fn, None, _C._ptr(pts), ctypes.c_int(n), ctypes.c_int(nb_neighbors),
-                                                  ctypes.c_double(std_ratio), _C._ptr(keep), _C._ptr(dist),
-                                                  _C._stream(pts.device))
-        _rc("statistical_outlier_mask", rc)
+        call("gsr_outlier_statistical", pts.device, pts, n, nb_neighbors, ctypes.c_double(std_ratio), keep, dist,
+             workspace=True, what="statistical_outlier_mask", errors=_ERRORS)
     return (keep.bool(), dist) if return_distances else keep.bool()
 
 
@@ -262,17 +212,13 @@ def normal_outlier_mask(points, normals, nb_neighbors=20, angle_threshold=math.p
         raise ValueError("normals must have one row per point")
     if not isinstance(nb_neighbors, int) or nb_neighbors < 1 or nb_neighbors > MAX_K:
         raise ValueError(f"nb_neighbors must be in [1, {MAX_K}], got {nb_neighbors}")
-    _on_rocm(points=pts, normals=nrm)
+    on_rocm(points=pts, normals=nrm)
     pts = pts.to(torch.float32).contiguous()
     keep = torch.zeros(n, dtype=torch.uint8, device=pts.device)
     if n:
         nrm = nrm.to(torch.float64).contiguous()
-        ws = _Workspace(pts.device)
-        with torch.cuda.device(pts.device):
-            rc = _C.lib().gsr_outlier_normal(ws.fn, None, _C._ptr(pts), _C._ptr(nrm), ctypes.c_int(n),
-                                             ctypes.c_int(nb_neighbors), ctypes.c_double(angle_threshold), _C._ptr(keep),
-                                             _C._stream(pts.device))
-        _rc("normal_outlier_mask", rc)
+        call("gsr_outlier_normal", pts.device, pts, nrm, n, nb_neighbors, ctypes.c_double(angle_threshold), keep,
+             workspace=True, what="normal_outlier_mask", errors=_ERRORS)
     return keep.bool()
 
 
@@ -283,7 +229,7 @@ def clean_point_cloud(points, normals, nb_neighbors=50, std_ratio=2.0, normal_ne
     nrm = _device_tensor("normals", normals, 3, (torch.float32, torch.float64))
     if nrm.shape[0] != pts.shape[0]:
         raise ValueError("normals must have one row per point")
-    _on_rocm(points=pts, normals=nrm)
+    on_rocm(points=pts, normals=nrm)
     first = torch.nonzero(statistical_outlier_mask(pts, nb_neighbors, std_ratio)).flatten()
     if first.numel() == 0:
         return first

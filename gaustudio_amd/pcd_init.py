@@ -18,9 +18,9 @@ import math
 import numpy as np
 import torch
 
-from . import _C
+from ._abi import call, on_rocm, same_device
 from .formats import GaussianCloud, read_ply_vertices
-from .pcd_fusion import _Workspace, _on_rocm, _rc
+from .pcd_fusion import _ERRORS
 from .postprocess import depth_to_points
 
 
@@ -41,12 +41,6 @@ def _sh_degree(sh_degree):
     if isinstance(sh_degree, bool) or int(sh_degree) != sh_degree or not 0 <= sh_degree <= 3:
         raise ValueError(f"sh_degree must be 0..3, got {sh_degree}")
     return int(sh_degree)
-
-
-def _same_device(dev, **tensors):
-    for name, t in tensors.items():
-        if t is not None and t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, the points on {dev}")
 
 
 def _ready(t):
@@ -73,16 +67,13 @@ def mean_dist2(points, return_stats=False, cell_target=None):
         raise ValueError("mean_dist2 takes fewer than 2^31 points")
     if cell_target is not None and (isinstance(cell_target, bool) or int(cell_target) != cell_target or not 1 <= cell_target <= 64):
         raise ValueError(f"cell_target must be in [1, 64], got {cell_target!r}")
-    _on_rocm(points=pts)
+    on_rocm(points=pts)
     pts = _ready(pts)
     out = torch.empty(n, dtype=torch.float32, device=pts.device)
     stats = (ctypes.c_int * 3)()
     ms = (ctypes.c_float * 3)() if return_stats else None
-    ws = _Workspace(pts.device)
-    with torch.cuda.device(pts.device):
-        rc = _C.lib().gsr_mean_dist3_ex(ws.fn, None, _C._ptr(pts), ctypes.c_int(n), _C._ptr(out), ctypes.c_int(int(cell_target or 0)),
-                                        stats, ms, _C._stream(pts.device))
-    _rc("mean_dist2", rc)
+    call("gsr_mean_dist3_ex", pts.device, pts, n, out, int(cell_target or 0), stats, ms, workspace=True, what="mean_dist2",
+         errors=_ERRORS)
     if not return_stats:
         return out
     return out, dict(occupied_cells=int(stats[0]), shell2_lanes=int(stats[1]), leftovers=int(stats[2]),
@@ -139,21 +130,16 @@ def point_seeds(xyz, rgb=None, scale=None, rot=None, normals=None, opacity=None,
         raise ValueError("point_seeds takes fewer than 2^31 points")
     if scale is None and dist2 is None and n < 4:
         raise ValueError(f"point_seeds without a scale needs at least 4 points (three neighbours each), got {n}")
-    _on_rocm(xyz=xyz, rgb=rgb, scale=scale, rot=rot, normals=normals, opacity=op_t, dist2=dist2)
+    on_rocm(xyz=xyz, rgb=rgb, scale=scale, rot=rot, normals=normals, opacity=op_t, dist2=dist2)
     dev = xyz.device
-    _same_device(dev, rgb=rgb, scale=scale, rot=rot, normals=normals, opacity=op_t, dist2=dist2)
+    same_device(dev, ref="the points", rgb=rgb, scale=scale, rot=rot, normals=normals, opacity=op_t, dist2=dist2)
     xyz, rgb, scale, rot, normals, op_t, dist2 = (_ready(t) for t in (xyz, rgb, scale, rot, normals, op_t, dist2))
     if scale is None and dist2 is None:
         dist2 = mean_dist2(xyz)
     op = default_opacity() if opacity is None else (0.0 if op_t is not None else float(opacity))
     new = lambda c: torch.empty((n, c), dtype=torch.float32, device=dev)
     o_xyz, f_dc, o_scale, o_rot, o_op = new(3), new(3), new(3), new(4), new(1)
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_point_seeds(_C._ptr(xyz), _C._ptr(rgb), _C._ptr(dist2), _C._ptr(scale), _C._ptr(rot), _C._ptr(normals),
-                                      _C._ptr(op_t), ctypes.c_float(op), ctypes.c_int(n), _C._ptr(o_xyz), _C._ptr(f_dc),
-                                      _C._ptr(o_scale), _C._ptr(o_rot), _C._ptr(o_op), _C._stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"gsr_point_seeds failed (rc={rc})")
+    call("gsr_point_seeds", dev, xyz, rgb, dist2, scale, rot, normals, op_t, ctypes.c_float(op), n, o_xyz, f_dc, o_scale, o_rot, o_op)
     return GaussianCloud(xyz=o_xyz, f_dc=f_dc.reshape(n, 1, 3),
                          f_rest=torch.zeros((n, (deg + 1) ** 2 - 1, 3), dtype=torch.float32, device=dev),
                          opacity=o_op, scale=o_scale, rot=o_rot)
@@ -284,22 +270,18 @@ def depth_seeds(frames, sh_degree=3):
     if total >= 2 ** 31:
         raise ValueError("depth_seeds: 2^31 pixels or more")
     for j, (depth, image, _, _) in enumerate(checked):
-        _on_rocm(**{f"frame {j}: depth": depth, f"frame {j}: image": image})
+        on_rocm(**{f"frame {j}: depth": depth, f"frame {j}: image": image})
     dev = checked[0][0].device
     new = lambda: torch.empty((total, 3), dtype=torch.float32, device=dev)
     xyz, rgb, scale = new(), new(), new()
     off = 0
     for j, (depth, image, K, E) in enumerate(checked):
-        _same_device(dev, **{f"frame {j}: depth": depth, f"frame {j}: image": image})
+        same_device(dev, ref="the points", **{f"frame {j}: depth": depth, f"frame {j}: image": image})
         n = depth.numel()
         if n == 0:
             continue
         depth, image = _ready(depth), _ready(image)
         pts = depth_to_points(depth, K, E, "world")
-        with torch.cuda.device(dev):
-            rc = _C.lib().gsr_depth_seed_pack(_C._ptr(pts), _C._ptr(image), _C._ptr(depth), ctypes.c_int(n), ctypes.c_float(_focal(K)),
-                                              _C._ptr(xyz[off:]), _C._ptr(rgb[off:]), _C._ptr(scale[off:]), _C._stream(dev))
-        if rc < 0:
-            raise RuntimeError(f"gsr_depth_seed_pack failed (rc={rc})")
+        call("gsr_depth_seed_pack", dev, pts, image, depth, n, ctypes.c_float(_focal(K)), xyz[off:], rgb[off:], scale[off:])
         off += n
     return point_seeds(xyz, rgb=rgb, scale=scale, opacity=0.0, sh_degree=deg)

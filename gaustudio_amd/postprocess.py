@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from . import _C
+from ._abi import call, on_rocm
 
 
 def _host16(t, n):
@@ -22,8 +22,7 @@ def _host16(t, n):
 def _check(depth):
     if depth.dim() != 2:
         raise ValueError("depth must have shape [H, W]")
-    if not depth.is_cuda:
-        raise RuntimeError(f"depth is on '{depth.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
+    on_rocm(depth=depth)
     if depth.dtype != torch.float32:
         raise RuntimeError("depth must be float32")
     return depth.contiguous()
@@ -35,16 +34,12 @@ def depth_to_points(depth, intrinsics, extrinsics=None, coordinate="camera"):
         raise ValueError("Invalid coordinate system.")
     depth = _check(depth)
     H, W = depth.shape
-    L = _C.lib()
     out = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
     K = _host16(intrinsics, 9)
     E = _host16(extrinsics, 16) if coordinate == "world" else None
     if coordinate == "world" and E is None:
         raise ValueError("extrinsics are required for world coordinates")
-    with torch.cuda.device(depth.device):
-        rc = L.gsr_depth_to_points(_C._ptr(depth), ctypes.c_int(W), ctypes.c_int(H), K, E, _C._ptr(out), _C._stream(depth.device))
-    if rc < 0:
-        raise RuntimeError(f"gsr_depth_to_points failed (rc={rc}): singular intrinsics / extrinsics?")
+    call("gsr_depth_to_points", depth.device, depth, W, H, K, E, out, hint=": singular intrinsics / extrinsics?")
     return out
 
 
@@ -54,17 +49,12 @@ def depth_to_normals(depth, intrinsics, extrinsics=None, k=3, d_min=1e-3, d_max=
         raise ValueError("Invalid coordinate system.")
     depth = _check(depth)
     H, W = depth.shape
-    L = _C.lib()
     out = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
     K = _host16(intrinsics, 9)
     E = _host16(extrinsics, 16) if coordinate == "world" else None
     if coordinate == "world" and E is None:
         raise ValueError("extrinsics are required for world coordinates")
-    with torch.cuda.device(depth.device):
-        rc = L.gsr_depth_to_normals(_C._ptr(depth), ctypes.c_int(W), ctypes.c_int(H), K, ctypes.c_int(int(k)),
-                                    ctypes.c_float(d_min), ctypes.c_float(d_max), E, _C._ptr(out), _C._stream(depth.device))
-    if rc < 0:
-        raise RuntimeError(f"gsr_depth_to_normals failed (rc={rc})")
+    call("gsr_depth_to_normals", depth.device, depth, W, H, K, int(k), ctypes.c_float(d_min), ctypes.c_float(d_max), E, out)
     return out
 
 
@@ -86,13 +76,8 @@ def depth_epilogue(depth, intrinsics, extrinsics=None, opacity=None, min_opacity
         raise ValueError("extrinsics are required for world coordinates")
     pts = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device) if want_points else None
     nrm = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device) if want_normals else None
-    L = _C.lib()
-    with torch.cuda.device(depth.device):
-        rc = L.gsr_depth_epilogue(_C._ptr(depth), _C._ptr(opacity), ctypes.c_float(float(min_opacity)), ctypes.c_int(W),
-                                  ctypes.c_int(H), K, ctypes.c_int(int(k)), ctypes.c_float(d_min), ctypes.c_float(d_max), E,
-                                  _C._ptr(pts), _C._ptr(nrm), _C._stream(depth.device))
-    if rc < 0:
-        raise RuntimeError(f"gsr_depth_epilogue failed (rc={rc}): k > 5, or singular intrinsics / extrinsics?")
+    call("gsr_depth_epilogue", depth.device, depth, opacity, ctypes.c_float(float(min_opacity)), W, H, K, int(k),
+         ctypes.c_float(d_min), ctypes.c_float(d_max), E, pts, nrm, hint=": k > 5, or singular intrinsics / extrinsics?")
     return pts, nrm
 
 
@@ -108,11 +93,6 @@ def masked_bilateral_filter(depth_map, mask, d=3, sigma_color=75, sigma_space=75
     out = torch.empty_like(depth)
     new_mask = torch.empty_like(m8)
     scratch = torch.empty(2, dtype=torch.int32, device=depth.device)
-    L = _C.lib()
-    with torch.cuda.device(depth.device):
-        rc = L.gsr_masked_bilateral(_C._ptr(depth), _C._ptr(m8), ctypes.c_int(W), ctypes.c_int(H), ctypes.c_int(int(d)),
-                                    ctypes.c_float(float(sigma_color)), ctypes.c_float(float(sigma_space)), _C._ptr(out),
-                                    _C._ptr(new_mask), _C._ptr(scratch), _C._stream(depth.device))
-    if rc < 0:
-        raise RuntimeError(f"gsr_masked_bilateral failed (rc={rc}): d must be odd")
+    call("gsr_masked_bilateral", depth.device, depth, m8, W, H, int(d), ctypes.c_float(float(sigma_color)),
+         ctypes.c_float(float(sigma_space)), out, new_mask, scratch, hint=": d must be odd")
     return out, new_mask.to(mask.dtype)

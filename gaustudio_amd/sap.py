@@ -19,8 +19,8 @@ import ctypes
 
 import torch
 
-from . import _C
-from .pcd_fusion import _Workspace, _device_tensor, _on_rocm, _rc
+from ._abi import Workspace, call, on_rocm
+from .pcd_fusion import _ERRORS, _device_tensor
 
 MAX_CHANNELS = 4
 
@@ -47,8 +47,8 @@ def _grid(name, grid):
     return _res(grid.shape)
 
 
-def _bad_points(what):
-    return ValueError(f"{what}: a point coordinate is not finite or lies outside [0, 1)")
+def _point_errors(what):
+    return {-2: f"{what}: a point coordinate is not finite or lies outside [0, 1)", **_ERRORS}
 
 
 def point_rasterize(pts, vals, size, weighted=True, return_counts=False):
@@ -64,7 +64,7 @@ def point_rasterize(pts, vals, size, weighted=True, return_counts=False):
     if vals.shape[0] != pts.shape[0]:
         raise ValueError("vals must have one row per point")
     res = _res(size)
-    _on_rocm(pts=pts, vals=vals)
+    on_rocm(pts=pts, vals=vals)
     if vals.device != pts.device:
         raise ValueError("pts and vals must be on the same device")
     dev = pts.device
@@ -72,14 +72,8 @@ def point_rasterize(pts, vals, size, weighted=True, return_counts=False):
     n, C = pts.shape[0], vals.shape[1]
     grid = torch.empty((C,) + res, dtype=torch.float32, device=dev)
     counts = torch.empty(res, dtype=torch.int32, device=dev) if return_counts else None
-    ws = _Workspace(dev)
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_psr_rasterize(ws.fn, None, _C._ptr(pts), ctypes.c_int(n), _C._ptr(vals), ctypes.c_int(C),
-                                        ctypes.c_int(res[0]), ctypes.c_int(res[1]), ctypes.c_int(res[2]),
-                                        ctypes.c_int(1 if weighted else 0), _C._ptr(grid), _C._ptr(counts), _C._stream(dev))
-    if rc == -2:
-        raise _bad_points("point_rasterize")
-    _rc("gsr_psr_rasterize", rc)
+    call("gsr_psr_rasterize", dev, pts, n, vals, C, *res, bool(weighted), grid, counts, workspace=True,
+         errors=_point_errors("point_rasterize"))
     return (grid, counts) if return_counts else grid
 
 
@@ -88,20 +82,14 @@ def _interp(grid, pts, want_mean):
     pts = _device_tensor("pts", pts, 3)
     if pts.shape[0] < 1:
         raise ValueError("grid_interp needs at least one point")
-    _on_rocm(grid=grid, pts=pts)
+    on_rocm(grid=grid, pts=pts)
     if grid.device != pts.device:
         raise ValueError("grid and pts must be on the same device")
     dev = pts.device
     grid, pts = grid.detach().contiguous(), pts.detach().contiguous()
     out = torch.empty(pts.shape[0], dtype=torch.float32, device=dev)
     mean = torch.empty(1, dtype=torch.float64, device=dev) if want_mean else None
-    ws = _Workspace(dev)
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_psr_interp(ws.fn, None, _C._ptr(grid), ctypes.c_int(res[0]), ctypes.c_int(res[1]), ctypes.c_int(res[2]),
-                                     _C._ptr(pts), ctypes.c_int(pts.shape[0]), _C._ptr(out), _C._ptr(mean), _C._stream(dev))
-    if rc == -2:
-        raise _bad_points("grid_interp")
-    _rc("gsr_psr_interp", rc)
+    call("gsr_psr_interp", dev, grid, *res, pts, pts.shape[0], out, mean, workspace=True, errors=_point_errors("grid_interp"))
     return out, mean
 
 
@@ -121,14 +109,11 @@ def spectral_solve(spectrum, size, sig):
         raise TypeError("spectrum must be a complex64 tensor")
     if tuple(spectrum.shape) != (3, res[0], res[1], res[2] // 2 + 1):
         raise ValueError(f"spectrum must have shape [3, {res[0]}, {res[1]}, {res[2] // 2 + 1}], got {list(spectrum.shape)}")
-    _on_rocm(spectrum=spectrum)
+    on_rocm(spectrum=spectrum)
     dev = spectrum.device
     spec = torch.view_as_real(spectrum.detach().contiguous())
     phi = torch.empty((res[0], res[1], res[2] // 2 + 1, 2), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_psr_spectral(_C._ptr(spec), ctypes.c_int(res[0]), ctypes.c_int(res[1]), ctypes.c_int(res[2]),
-                                       ctypes.c_double(float(sig)), _C._ptr(phi), _C._stream(dev))
-    _rc("gsr_psr_spectral", rc)
+    call("gsr_psr_spectral", dev, spec, *res, ctypes.c_double(float(sig)), phi, errors=_ERRORS)
     return torch.view_as_complex(phi)
 
 
@@ -136,18 +121,15 @@ def normalize_grid(grid, mean=None, scale=True, apply_tanh=False):
     """The tail of DPSR.forward in one pass: grid - float32(mean) when mean (float64 [1] device tensor) is given, then with
     scale -v / |v[0,0,0]| * 0.5 (v[0,0,0] after the shift), then with apply_tanh tanh(v).  Returns a new tensor."""
     _grid("grid", grid)
-    _on_rocm(grid=grid, mean=mean)
+    on_rocm(grid=grid, mean=mean)
     dev = grid.device
     if mean is not None and (mean.dtype != torch.float64 or mean.numel() != 1 or mean.device != dev):
         raise ValueError("mean must be a float64 tensor with one element on the device of grid")
     grid = grid.detach().contiguous()
     out = torch.empty_like(grid)
     params = torch.empty(2, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_psr_normalize(_C._ptr(grid), _C._ptr(out), ctypes.c_longlong(grid.numel()), _C._ptr(mean),
-                                        ctypes.c_int(1 if scale else 0), ctypes.c_int(1 if apply_tanh else 0), _C._ptr(params),
-                                        _C._stream(dev))
-    _rc("gsr_psr_normalize", rc)
+    call("gsr_psr_normalize", dev, grid, out, ctypes.c_longlong(grid.numel()), mean, bool(scale), bool(apply_tanh), params,
+         errors=_ERRORS)
     return out
 
 
@@ -177,7 +159,7 @@ class DPSR:
         N = _device_tensor("N", N, 3)
         if V.shape[0] < 1:
             raise ValueError("DPSR needs at least one point")       # no samples to shift by, and 0 / 0 in the scaling
-        _on_rocm(V=V, N=N)
+        on_rocm(V=V, N=N)
         with torch.no_grad():
             ras = point_rasterize(V, N, self.res, weighted=self.weighted)
             spec = torch.fft.rfftn(ras, dim=(1, 2, 3))
@@ -197,7 +179,7 @@ def marching_cubes(grid, level=0.0):
     vertex per crossing edge, at i + (level - a) / (b - a) in fp32; vertices ordered by (lower node of the edge, axis),
     triangles by (cube, table order).  Watertight away from the grid boundary and deterministic by construction."""
     res = _grid("grid", grid)
-    _on_rocm(grid=grid)
+    on_rocm(grid=grid)
     dev = grid.device
     grid = grid.detach().contiguous()
     nn = res[0] * res[1] * res[2]
@@ -205,18 +187,13 @@ def marching_cubes(grid, level=0.0):
     voff = torch.empty(nn + 1, dtype=torch.int32, device=dev)
     toff = torch.empty(nn + 1, dtype=torch.int32, device=dev)
     nv, nt = ctypes.c_int(0), ctypes.c_int(0)
-    r = [ctypes.c_int(v) for v in res]
-    L = _C.lib()
-    ws = _Workspace(dev)
+    ws = Workspace(dev)                 # released when the mesh is returned
     with torch.cuda.device(dev):
-        st = _C._stream(dev)
-        _rc("gsr_psr_mc_classify", L.gsr_psr_mc_classify(ws.fn, None, _C._ptr(grid), r[0], r[1], r[2], ctypes.c_float(level),
-                                                          _C._ptr(info), _C._ptr(voff), _C._ptr(toff), ctypes.byref(nv),
-                                                          ctypes.byref(nt), st))
+        call("gsr_psr_mc_classify", dev, grid, *res, ctypes.c_float(level), info, voff, toff, ctypes.byref(nv), ctypes.byref(nt),
+             workspace=ws, errors=_ERRORS)
         verts = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
         faces = torch.empty((nt.value, 3), dtype=torch.int32, device=dev)
-        _rc("gsr_psr_mc_emit", L.gsr_psr_mc_emit(_C._ptr(grid), r[0], r[1], r[2], ctypes.c_float(level), _C._ptr(info),
-                                                  _C._ptr(voff), _C._ptr(toff), _C._ptr(verts), _C._ptr(faces), st))
+        call("gsr_psr_mc_emit", dev, grid, *res, ctypes.c_float(level), info, voff, toff, verts, faces, errors=_ERRORS)
     return verts, faces
 
 
@@ -256,7 +233,7 @@ class ShapeAsPoints:
             raise ValueError("normals must have one row per point")
         if points.shape[0] < 1:
             raise ValueError("ShapeAsPoints needs at least one point")
-        _on_rocm(points=points, normals=normals)
+        on_rocm(points=points, normals=normals)
         if normals.device != points.device:
             raise ValueError("points and normals must be on the same device")
         self = cls(**conf)

@@ -12,11 +12,9 @@ its lookup about one pixel off, vertices behind the camera): INTEGRATION.md s21.
 own pixel instead.  The result feeds formats.write_ply_mesh(vertex_colors=...), voxelize.voxel_seeds(colors="closest") and
 mesh_init.mesh_seeds.  Forward only, deterministic, no CPU fallback; every call runs on the current stream of the mesh's device.
 """
-import ctypes
-
 import torch
 
-from . import _C
+from ._abi import call, on_rocm, same_device
 from .mesh_raster import MeshRasterizer, _host_f32
 from .voxelize import _mesh
 
@@ -24,11 +22,7 @@ SAMPLING = ("reference", "exact")
 COS_LIMIT = -0.05                   # texture_mesh.py:121
 
 
-def _rc(name, rc):
-    if rc == -2:
-        raise ValueError(f"{name}: invalid argument (a bad size, a matrix that is not finite or singular intrinsics)")
-    if rc < 0:
-        raise RuntimeError(f"{name} failed (rc={rc})")
+_ERRORS = {-2: "{what}: invalid argument (a bad size, a matrix that is not finite or singular intrinsics)"}
 
 
 class BakeStats:
@@ -63,10 +57,8 @@ def _image(image, dev):
         raise TypeError(f"image must be float32 or uint8, got {image.dtype}")
     if image.dim() != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
         raise ValueError(f"image must have shape [H, W, 3], got {list(image.shape)}")
-    if image.device.type != "cuda":
-        raise ValueError(f"image is on '{image.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
-    if image.device != dev:
-        raise ValueError(f"image is on {image.device}, the mesh on {dev}")
+    on_rocm(ValueError, image=image)
+    same_device(dev, image=image)
     if image.dtype == torch.uint8:
         image = image.to(torch.float32) / 255.0
     return image.detach().contiguous()
@@ -97,16 +89,12 @@ class TextureBaker:
         r = self.raster
         if not torch.is_tensor(visible) or visible.dtype not in (torch.bool, torch.uint8) or tuple(visible.shape) != (r.num_faces,):
             raise TypeError(f"visible must be a bool or uint8 tensor of shape [{r.num_faces}]")
-        if visible.device != self.device:
-            raise ValueError(f"visible is on {visible.device}, the mesh on {self.device}")
+        same_device(self.device, visible=visible)
         E = _host_f32("extrinsics", extrinsics, (4, 4))
         vis = visible.to(torch.uint8).contiguous()
         cos = torch.empty(r.num_faces, dtype=torch.float32, device=self.device) if return_cos else None
-        with torch.cuda.device(self.device):
-            rc = _C.lib().gsr_mesh_bake_select(_C._ptr(r.verts), ctypes.c_int(r.num_verts), _C._ptr(r.faces), ctypes.c_int(r.num_faces),
-                                               _C._ptr(vis), E, ctypes.c_int(int(seq)), _C._ptr(self._stamp), _C._ptr(cos),
-                                               _C._stream(self.device))
-        _rc("gsr_mesh_bake_select", rc)
+        call("gsr_mesh_bake_select", self.device, r.verts, r.num_verts, r.faces, r.num_faces, vis, E, int(seq), self._stamp, cos,
+             errors=_ERRORS)
         return cos
 
     def sample(self, image, intrinsics, extrinsics, seq):
@@ -115,12 +103,8 @@ class TextureBaker:
         K = _host_f32("intrinsics", intrinsics, (3, 3))
         E = _host_f32("extrinsics", extrinsics, (4, 4))
         r = self.raster
-        with torch.cuda.device(self.device):
-            rc = _C.lib().gsr_mesh_bake_sample(_C._ptr(r.verts), ctypes.c_int(r.num_verts), _C._ptr(self._stamp), ctypes.c_int(int(seq)),
-                                               K, E, _C._ptr(img), ctypes.c_int(img.shape[0]), ctypes.c_int(img.shape[1]),
-                                               ctypes.c_int(int(self.sampling == "exact")), _C._ptr(self.vertex_colors),
-                                               _C._ptr(self.baked_by), _C._stream(self.device))
-        _rc("gsr_mesh_bake_sample", rc)
+        call("gsr_mesh_bake_sample", self.device, r.verts, r.num_verts, self._stamp, int(seq), K, E, img, img.shape[0], img.shape[1],
+             self.sampling == "exact", self.vertex_colors, self.baked_by, errors=_ERRORS)
 
     def add_view(self, image, intrinsics, extrinsics, strict=True):
         """One iteration of texture_mesh.py:76-141.  image [H,W,3] float32 in [0,1] (or uint8), intrinsics [3,3], extrinsics

@@ -14,27 +14,19 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _C
+from ._abi import call
+from ._block_volume import BlockVolume
 
-_EMPTY = -1          # all bits set, as int64
 
-
-class TSDFVolume:
+class TSDFVolume(BlockVolume):
     def __init__(self, voxel_size, sdf_trunc, space_carving=False, device="cuda", capacity_blocks=1 << 18):
         """capacity_blocks: hash slots (power of two).  Every slot reserves 512 voxels x 8 B = 4 KiB of HBM, so the
         default 2^18 slots = 1 GiB holds scenes of ~130 k occupied 8^3 blocks at a load factor of 0.5."""
         self.voxel_size = float(voxel_size)
         self.sdf_trunc = float(sdf_trunc)
         self.space_carving = bool(space_carving)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"TSDFVolume lives on a ROCm device, got '{self.device}' (no CPU fallback)")
-        if capacity_blocks & (capacity_blocks - 1) or capacity_blocks <= 0:
-            raise ValueError("capacity_blocks must be a power of two")
-        self.capacity = int(capacity_blocks)
-        self.keys = torch.full((self.capacity,), _EMPTY, dtype=torch.int64, device=self.device)
-        self.voxels = torch.zeros((self.capacity, 512), dtype=torch.int64, device=self.device)
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        super().__init__(device, capacity_blocks)
+        self._alloc(512, dtype=torch.int64)
 
     # ------------------------------------------------------------------ integrate
     def integrate(self, points, extrinsic=None, origin=None):
@@ -61,15 +53,8 @@ class TSDFVolume:
         if pts.shape[0] == 0:
             return
         origin_c = (ctypes.c_float * 3)(*[float(v) for v in o])
-        L = _C.lib()
-        with torch.cuda.device(self.device):
-            rc = L.gsr_tsdf_integrate_map(_C._ptr(pts), ctypes.c_int(pts.shape[0]), ctypes.c_int(row_w), origin_c,
-                                          ctypes.c_float(self.voxel_size), ctypes.c_float(self.sdf_trunc),
-                                          ctypes.c_int(int(self.space_carving)), _C._ptr(self.keys),
-                                          ctypes.c_uint64(self.capacity), _C._ptr(self.voxels), _C._ptr(self.status),
-                                          _C._stream(self.device))
-        if rc < 0:
-            raise RuntimeError(f"gsr_tsdf_integrate_map failed (rc={rc})")
+        call("gsr_tsdf_integrate_map", self.device, pts, pts.shape[0], row_w, origin_c, ctypes.c_float(self.voxel_size),
+             ctypes.c_float(self.sdf_trunc), self.space_carving, self.keys, ctypes.c_uint64(self.capacity), self.voxels, self.status)
 
     def _check_overflow(self):
         st = int(self.status.item())
@@ -81,17 +66,6 @@ class TSDFVolume:
                                "voxel word is full); later observations of it were dropped")
 
     # ------------------------------------------------------------------ inspection
-    def occupied_blocks(self):
-        """(slots [n] int32, block coordinates [n,3] int32), ordered by block key (deterministic)."""
-        self._check_overflow()
-        slots = torch.nonzero(self.keys != _EMPTY).flatten()
-        k = self.keys[slots]
-        k, order = torch.sort(k)
-        slots = slots[order]
-        B = 1 << 20
-        coords = torch.stack([((k >> 42) & 0x1fffff) - B, ((k >> 21) & 0x1fffff) - B, (k & 0x1fffff) - B], dim=1)
-        return slots.to(torch.int32).contiguous(), coords.to(torch.int32)
-
     def export_voxels(self):
         """All observed voxels as (coords [m,3] int32, tsdf [m] f32, weight [m] int32, sum_q [m] int64), sorted by
         (z, y, x).  Test / inspection helper."""
@@ -101,20 +75,8 @@ class TSDFVolume:
         tsdf = torch.empty((n, 512), dtype=torch.float32, device=self.device)
         sums = torch.empty((n, 512), dtype=torch.int64, device=self.device)
         if n:
-            L = _C.lib()
-            with torch.cuda.device(self.device):
-                rc = L.gsr_tsdf_export_blocks(_C._ptr(self.voxels), _C._ptr(slots), ctypes.c_int(n), ctypes.c_float(self.sdf_trunc),
-                                              _C._ptr(counts), _C._ptr(tsdf), _C._ptr(sums), _C._stream(self.device))
-            if rc < 0:
-                raise RuntimeError(f"gsr_tsdf_export_blocks failed (rc={rc})")
-        local = torch.arange(512, device=self.device)
-        lx, ly, lz = local & 7, (local >> 3) & 7, local >> 6
-        coords = bcoords[:, None, :] * 8 + torch.stack([lx, ly, lz], dim=1)[None].to(torch.int32)
-        m = counts > 0
-        coords, tsdf, counts, sums = coords[m], tsdf[m], counts[m], sums[m]
-        key = (coords[:, 2].long() << 42) + (coords[:, 1].long() << 21) + coords[:, 0].long()
-        order = torch.argsort(key)
-        return coords[order], tsdf[order], counts[order], sums[order]
+            call("gsr_tsdf_export_blocks", self.device, self.voxels, slots, n, ctypes.c_float(self.sdf_trunc), counts, tsdf, sums)
+        return self._sorted_voxels(bcoords, counts > 0, tsdf, counts, sums)
 
     # ------------------------------------------------------------------ mesh
     def extract_triangle_mesh(self, fill_holes=True, min_weight=0.5):
@@ -133,42 +95,6 @@ class TSDFVolume:
         return vertices, triangles
 
     def _extract_triangle_mesh_device(self, fill_holes, min_weight):
-        slots, _ = self.occupied_blocks()
-        n = slots.shape[0]
-        dev = self.device
-        if n == 0:
-            return torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev)
-        slot_to_block = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
-        slot_to_block[slots.long()] = torch.arange(n, dtype=torch.int32, device=dev)
-        cases = torch.empty((n, 512), dtype=torch.uint8, device=dev)
-        flags = torch.empty((n, 512), dtype=torch.int32, device=dev)
-        bnv = torch.empty(n, dtype=torch.int32, device=dev)
-        bnt = torch.empty(n, dtype=torch.int32, device=dev)
-        L = _C.lib()
-        cap = ctypes.c_uint64(self.capacity)
-        with torch.cuda.device(dev):
-            st = _C._stream(dev)
-            rc = L.gsr_tsdf_mc_classify(_C._ptr(self.keys), cap, _C._ptr(self.voxels), _C._ptr(slots), ctypes.c_int(n),
-                                        _C._ptr(slot_to_block), ctypes.c_float(self.sdf_trunc), ctypes.c_float(float(min_weight)),
-                                        ctypes.c_int(int(bool(fill_holes))), _C._ptr(cases), _C._ptr(flags), _C._ptr(bnv),
-                                        _C._ptr(bnt), st)
-            if rc < 0:
-                raise RuntimeError(f"gsr_tsdf_mc_classify failed (rc={rc})")
-            voff = torch.cumsum(bnv.long(), 0)
-            toff = torch.cumsum(bnt.long(), 0)
-            nv, nt = int(voff[-1].item()), int(toff[-1].item())
-            if nv >= 2 ** 31 or nt >= 2 ** 31:
-                raise RuntimeError("mesh too large for 32-bit indices")
-            voff = (voff - bnv).to(torch.int32).contiguous()
-            toff = (toff - bnt).to(torch.int32).contiguous()
-            vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-            triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
-            vbase = torch.empty((n, 512), dtype=torch.int32, device=dev)
-            if nt:
-                rc = L.gsr_tsdf_mc_emit(_C._ptr(self.keys), cap, _C._ptr(self.voxels), _C._ptr(slots), ctypes.c_int(n),
-                                        _C._ptr(slot_to_block), ctypes.c_float(self.voxel_size), ctypes.c_float(self.sdf_trunc),
-                                        _C._ptr(cases), _C._ptr(flags), _C._ptr(voff), _C._ptr(toff), _C._ptr(vbase),
-                                        _C._ptr(vertices), _C._ptr(triangles), st)
-                if rc < 0:
-                    raise RuntimeError(f"gsr_tsdf_mc_emit failed (rc={rc})")
-        return vertices, triangles
+        return self._marching_cubes(
+            "gsr_tsdf_mc_classify", (ctypes.c_float(self.sdf_trunc), ctypes.c_float(float(min_weight)), bool(fill_holes)),
+            "gsr_tsdf_mc_emit", (ctypes.c_float(self.voxel_size), ctypes.c_float(self.sdf_trunc)))

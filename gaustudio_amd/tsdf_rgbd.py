@@ -21,9 +21,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _C
-
-_EMPTY = -1          # all bits set, as int64
+from ._abi import call
+from ._block_volume import BlockVolume
 
 
 def _intrinsic4(intrinsic):
@@ -51,7 +50,7 @@ def _c_floats(a):
     return (ctypes.c_float * a.size)(*[float(v) for v in a.ravel()])
 
 
-class ColorTSDFVolume:
+class ColorTSDFVolume(BlockVolume):
     def __init__(self, voxel_length=0.02, sdf_trunc=0.04, depth_sampling_stride=4, device="cuda", capacity_blocks=1 << 16):
         """capacity_blocks: hash slots (power of two).  Every slot reserves 5 planes x 512 voxels x 4 B = 10 KiB of HBM, so
         the default 2^16 slots = 640 MiB.  depth_sampling_stride: every stride-th pixel of a depth image allocates blocks
@@ -59,21 +58,14 @@ class ColorTSDFVolume:
         self.voxel_length = float(voxel_length)
         self.sdf_trunc = float(sdf_trunc)
         self.depth_sampling_stride = int(depth_sampling_stride)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"ColorTSDFVolume lives on a ROCm device, got '{self.device}' (no CPU fallback)")
-        if capacity_blocks & (capacity_blocks - 1) or capacity_blocks <= 0:
-            raise ValueError("capacity_blocks must be a power of two")
+        super().__init__(device, capacity_blocks)
         if not self.voxel_length > 0 or not self.sdf_trunc > 0 or self.depth_sampling_stride < 1:
             raise ValueError("voxel_length and sdf_trunc must be positive, depth_sampling_stride at least 1")
         if self.sdf_trunc > 16 * self.voxel_length:
             raise ValueError("sdf_trunc is limited to 16 voxel lengths (a pixel then opens at most 5^3 blocks)")
-        self.capacity = int(capacity_blocks)
-        self.keys = torch.full((self.capacity,), _EMPTY, dtype=torch.int64, device=self.device)
+        self._alloc(5, 512, dtype=torch.float32)
         self.device = self.keys.device   # "cuda" resolved to the current device's index: images are compared against it
-        self.voxels = torch.zeros((self.capacity, 5, 512), dtype=torch.float32, device=self.device)
         self.stamp = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.frames = 0
         self.lane_filter = True          # tools/tsdf_rgbd_timing.py switches it off to measure it
         self.counters = None             # int64 [2] device tensor: the touch kernel counts its insertions there
@@ -119,31 +111,22 @@ class ColorTSDFVolume:
         if H == 0 or W == 0:
             return
         self.frames += 1
-        L = _C.lib()
         Kc, Ec, Eic = _c_floats(K), _c_floats(E), _c_floats(Einv)
         trunc, vl, st = ctypes.c_float(float(depth_trunc)), ctypes.c_float(self.voxel_length), ctypes.c_float(self.sdf_trunc)
         with torch.cuda.device(self.device):
-            stream = _C._stream(self.device)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.timings is not None else None
             if ev:
                 ev[0].record()
-            rc = L.gsr_ctsdf_touch(_C._ptr(depth), ctypes.c_int(W), ctypes.c_int(H), ctypes.c_int(self.depth_sampling_stride), Kc, Eic,
-                                   trunc, vl, st, _C._ptr(self.keys), ctypes.c_uint64(self.capacity), _C._ptr(self.stamp),
-                                   ctypes.c_int(self.frames), _C._ptr(self.status), ctypes.c_int(int(self.lane_filter)),
-                                   _C._ptr(self.counters), stream)
-            if rc < 0:
-                raise RuntimeError(f"gsr_ctsdf_touch failed (rc={rc})")
+            call("gsr_ctsdf_touch", self.device, depth, W, H, self.depth_sampling_stride, Kc, Eic, trunc, vl, st, self.keys,
+                 ctypes.c_uint64(self.capacity), self.stamp, self.frames, self.status, int(self.lane_filter), self.counters)
             if ev:
                 ev[1].record()
             touched = torch.nonzero(self.stamp == self.frames).flatten().to(torch.int32)
             self.last_touched = int(touched.shape[0])
             if ev:
                 ev[2].record()
-            rc = L.gsr_ctsdf_integrate(_C._ptr(depth), _C._ptr(color), ctypes.c_int(mode), ctypes.c_int(W), ctypes.c_int(H), Kc, Ec,
-                                       trunc, vl, st, _C._ptr(self.keys), _C._ptr(touched), ctypes.c_int(self.last_touched),
-                                       _C._ptr(self.voxels), stream)
-            if rc < 0:
-                raise RuntimeError(f"gsr_ctsdf_integrate failed (rc={rc})")
+            call("gsr_ctsdf_integrate", self.device, depth, color, mode, W, H, Kc, Ec, trunc, vl, st, self.keys, touched,
+                 self.last_touched, self.voxels)
             if ev:
                 ev[3].record()
                 torch.cuda.synchronize(self.device)
@@ -156,17 +139,6 @@ class ColorTSDFVolume:
                                "create the volume with a larger capacity_blocks")
 
     # ------------------------------------------------------------------ inspection
-    def occupied_blocks(self):
-        """(slots [n] int32, block coordinates [n,3] int32), ordered by block key (deterministic)."""
-        self._check_overflow()
-        slots = torch.nonzero(self.keys != _EMPTY).flatten()
-        k = self.keys[slots]
-        k, order = torch.sort(k)
-        slots = slots[order]
-        B = 1 << 20
-        coords = torch.stack([((k >> 42) & 0x1fffff) - B, ((k >> 21) & 0x1fffff) - B, (k & 0x1fffff) - B], dim=1)
-        return slots.to(torch.int32).contiguous(), coords.to(torch.int32)
-
     def export_voxels(self):
         """All observed voxels (weight > 0) as (coords [m,3] int32, tsdf [m] f32, weight [m] f32, color [m,3] f32 in 0..255),
         sorted by (z, y, x).  Test / inspection helper."""
@@ -176,19 +148,8 @@ class ColorTSDFVolume:
         weight = torch.empty((n, 512), dtype=torch.float32, device=self.device)
         color = torch.empty((n, 512, 3), dtype=torch.float32, device=self.device)
         if n:
-            with torch.cuda.device(self.device):
-                rc = _C.lib().gsr_ctsdf_export_blocks(_C._ptr(self.voxels), _C._ptr(slots), ctypes.c_int(n), _C._ptr(tsdf),
-                                                      _C._ptr(weight), _C._ptr(color), _C._stream(self.device))
-            if rc < 0:
-                raise RuntimeError(f"gsr_ctsdf_export_blocks failed (rc={rc})")
-        local = torch.arange(512, device=self.device)
-        lx, ly, lz = local & 7, (local >> 3) & 7, local >> 6
-        coords = bcoords[:, None, :] * 8 + torch.stack([lx, ly, lz], dim=1)[None].to(torch.int32)
-        m = weight > 0
-        coords, tsdf, weight, color = coords[m], tsdf[m], weight[m], color[m]
-        key = (coords[:, 2].long() << 42) + (coords[:, 1].long() << 21) + coords[:, 0].long()
-        order = torch.argsort(key)
-        return coords[order], tsdf[order], weight[order], color[order]
+            call("gsr_ctsdf_export_blocks", self.device, self.voxels, slots, n, tsdf, weight, color)
+        return self._sorted_voxels(bcoords, weight > 0, tsdf, weight, color)
 
     # ------------------------------------------------------------------ mesh
     def extract_triangle_mesh(self, min_weight=0.0, clean_ratio=None, with_normals=False):
@@ -215,58 +176,8 @@ class ColorTSDFVolume:
         return vertices, triangles, colors, normals
 
     def _extract_triangle_mesh_device(self, min_weight, timings=None):
-        slots, _ = self.occupied_blocks()
-        n = slots.shape[0]
-        dev = self.device
-        if n == 0:
-            z = lambda dt: torch.zeros((0, 3), dtype=dt, device=dev)
-            return z(torch.float32), z(torch.int32), z(torch.float32)
-        slot_to_block = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
-        slot_to_block[slots.long()] = torch.arange(n, dtype=torch.int32, device=dev)
-        cases = torch.empty((n, 512), dtype=torch.uint8, device=dev)
-        flags = torch.empty((n, 512), dtype=torch.int32, device=dev)
-        bnv = torch.empty(n, dtype=torch.int32, device=dev)
-        bnt = torch.empty(n, dtype=torch.int32, device=dev)
-        L = _C.lib()
-        cap = ctypes.c_uint64(self.capacity)
-        with torch.cuda.device(dev):
-            st = _C._stream(dev)
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
-            if ev:
-                ev[0].record()
-            rc = L.gsr_ctsdf_mc_classify(_C._ptr(self.keys), cap, _C._ptr(self.voxels), _C._ptr(slots), ctypes.c_int(n),
-                                         _C._ptr(slot_to_block), ctypes.c_float(float(min_weight)), _C._ptr(cases), _C._ptr(flags),
-                                         _C._ptr(bnv), _C._ptr(bnt), st)
-            if rc < 0:
-                raise RuntimeError(f"gsr_ctsdf_mc_classify failed (rc={rc})")
-            if ev:
-                ev[1].record()
-            voff = torch.cumsum(bnv.long(), 0)
-            toff = torch.cumsum(bnt.long(), 0)
-            nv, nt = int(voff[-1].item()), int(toff[-1].item())
-            if nv >= 2 ** 31 or nt >= 2 ** 31:
-                raise RuntimeError("mesh too large for 32-bit indices")
-            voff = (voff - bnv).to(torch.int32).contiguous()
-            toff = (toff - bnt).to(torch.int32).contiguous()
-            vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-            colors = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-            triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
-            vbase = torch.empty((n, 512), dtype=torch.int32, device=dev)
-            if ev:
-                ev[2].record()
-            if nt:
-                rc = L.gsr_ctsdf_mc_emit(_C._ptr(self.keys), cap, _C._ptr(self.voxels), _C._ptr(slots), ctypes.c_int(n),
-                                         _C._ptr(slot_to_block), ctypes.c_float(self.voxel_length), _C._ptr(cases), _C._ptr(flags),
-                                         _C._ptr(voff), _C._ptr(toff), _C._ptr(vbase), _C._ptr(vertices), _C._ptr(colors),
-                                         _C._ptr(triangles), st)
-                if rc < 0:
-                    raise RuntimeError(f"gsr_ctsdf_mc_emit failed (rc={rc})")
-            if ev:
-                ev[3].record()
-                torch.cuda.synchronize(dev)
-                timings["classify_ms"] = ev[0].elapsed_time(ev[1])
-                timings["emit_ms"] = ev[2].elapsed_time(ev[3])
-        return vertices, triangles, colors
+        return self._marching_cubes("gsr_ctsdf_mc_classify", (ctypes.c_float(float(min_weight)),),
+                                    "gsr_ctsdf_mc_emit", (ctypes.c_float(self.voxel_length),), vertex_extras=1, timings=timings)
 
 
 def _frame_parts(frame):

@@ -19,7 +19,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _C
+from ._abi import call, on_rocm
 from .formats import CameraRecord, GaussianCloud
 
 MASK_DTYPES = (torch.uint8, torch.bool, torch.float32)
@@ -111,8 +111,7 @@ def _check_masks(triples, masks):
     for n, m in enumerate(masks):
         if m is None:
             continue
-        if m.device.type != "cuda":
-            raise ValueError(f"mask {n} is on '{m.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
+        on_rocm(ValueError, **{f"mask {n}": m})
         if dev is not None and m.device != dev:
             raise ValueError(f"mask {n} is on {m.device}, an earlier mask on {dev}")
         dev = m.device
@@ -140,18 +139,11 @@ def pack_masks(masks, sizes=None, device=None):
     if total >= 2 ** 32:
         raise ValueError("the packed masks exceed 2^32 words")
     words = torch.empty(total, dtype=torch.int32, device=dev)
-    L = _C.lib()
-    with torch.cuda.device(dev):
-        st = _C._stream(dev)
-        for m, lay in zip(masks, layout):
-            if lay is None or m.numel() == 0:
-                continue
-            m = m.contiguous()
-            rc = L.gsr_hull_pack_masks(_C._ptr(m), ctypes.c_int(1 if m.dtype == torch.float32 else 0), ctypes.c_int(m.shape[1]),
-                                       ctypes.c_int(m.shape[0]), _C._ptr(words), ctypes.c_uint64(lay[0]), ctypes.c_int(lay[1]),
-                                       ctypes.c_uint64(total), st)
-            if rc < 0:
-                raise RuntimeError(f"gsr_hull_pack_masks failed (rc={rc})")
+    for m, lay in zip(masks, layout):
+        if lay is None or m.numel() == 0:
+            continue
+        call("gsr_hull_pack_masks", dev, m.contiguous(), m.dtype == torch.float32, m.shape[1], m.shape[0], words,
+             ctypes.c_uint64(lay[0]), lay[1], ctypes.c_uint64(total))
     return words, layout
 
 
@@ -186,13 +178,8 @@ def carve_axes(cameras, masks, axes, return_carved_by=False, device=None, packed
     filled = torch.empty((R0, R1, R2), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     carved_by = torch.empty((R0, R1, R2), dtype=torch.int32, device=dev) if return_carved_by else None
-    with torch.cuda.device(dev):
-        rc = _C.lib().gsr_hull_carve(_C._ptr(axd[0]), _C._ptr(axd[1]), _C._ptr(axd[2]), ctypes.c_int(R0), ctypes.c_int(R1),
-                                     ctypes.c_int(R2), table, _C._ptr(table_dev), ctypes.c_int(len(triples)), _C._ptr(words),
-                                     ctypes.c_uint64(words.numel()), _C._ptr(filled), _C._ptr(count), _C._ptr(carved_by),
-                                     _C._stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"gsr_hull_carve failed (rc={rc})")
+    call("gsr_hull_carve", dev, *axd, R0, R1, R2, table, table_dev, len(triples), words, ctypes.c_uint64(words.numel()), filled,
+         count, carved_by)
     return filled.bool(), int(count.item()), carved_by
 
 

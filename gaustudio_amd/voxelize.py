@@ -21,9 +21,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _C
+from ._abi import Workspace, call, check_mesh, on_rocm, same_device
 from .formats import GaussianCloud
-from .pcd_fusion import _Workspace
 
 MAX_RES = 1024                      # GSR_VOXEL_MAX_RES
 C0 = 0.28209479177387814            # gaustudio/utils/sh_utils.py
@@ -57,28 +56,10 @@ def _mesh(vertices, faces, vertex_colors=None, vertex_dtypes=(torch.float32, tor
     """Shapes and dtypes first, then devices, so that those errors need no GPU.  Returns the device."""
     if not torch.is_tensor(vertices) or not torch.is_tensor(faces):
         raise TypeError("vertices and faces must be torch tensors")
-    if vertices.dtype not in vertex_dtypes:
-        raise TypeError(f"vertices must be one of {[str(d) for d in vertex_dtypes]}, got {vertices.dtype}")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"faces must be int32 or int64, got {faces.dtype}")
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must have shape [V, 3], got {list(vertices.shape)}")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces must have shape [F, 3], got {list(faces.shape)}")
-    if vertices.shape[0] >= 2 ** 28 or faces.shape[0] >= 2 ** 28:
-        raise ValueError("the mesh must have fewer than 2^28 vertices and faces")
-    if vertex_colors is not None:
-        if not torch.is_tensor(vertex_colors):
-            raise TypeError("vertex_colors must be a torch tensor or None")
-        if vertex_colors.dtype != torch.float32:
-            raise TypeError(f"vertex_colors must be float32, got {vertex_colors.dtype}")
-        if tuple(vertex_colors.shape) != tuple(vertices.shape):
-            raise ValueError(f"vertex_colors must have shape {list(vertices.shape)} like vertices, got {list(vertex_colors.shape)}")
-    for name, t in (("vertices", vertices), ("faces", faces), ("vertex_colors", vertex_colors)):
-        if t is not None and t.device.type != "cuda":
-            raise ValueError(f"{name} is on '{t.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
-        if t is not None and t.device != vertices.device:
-            raise ValueError(f"{name} is on {t.device}, vertices on {vertices.device}")
+    limit = "the mesh must have fewer than 2^28 vertices and faces"
+    check_mesh(vertices, faces, vertex_colors, vertex_dtypes=vertex_dtypes, max_verts=(2 ** 28, limit), max_faces=(2 ** 28, limit),
+               device_exc=ValueError)
+    same_device(vertices.device, ref="vertices", faces=faces, vertex_colors=vertex_colors)
     return vertices.device
 
 
@@ -104,25 +85,9 @@ def _bounds(voxel_size, min_bound, max_bound):
     return vs, lo, hi, shape
 
 
-def _rc(name, rc, arg_error):
-    if rc == -2:
-        raise ValueError(f"{name}: {arg_error}")
-    if rc < 0:
-        raise RuntimeError(f"{name} failed (rc={rc})")
-
-
-class _Call:
-    """The arguments every gsr_voxel_* entry shares."""
-
-    def __init__(self, vs, lo, shape, dev):
-        self.vs = ctypes.c_double(vs)
-        self.mb = (ctypes.c_double * 3)(*lo)
-        self.n = [ctypes.c_int(v) for v in shape]
-        self.dev = dev
-        self.L = _C.lib()
-
-    def grid(self):
-        return (self.vs, self.mb, *self.n)
+def _grid_args(vs, lo, shape):
+    """The arguments every gsr_voxel_* entry shares: voxel size, min bound, n0, n1, n2."""
+    return (ctypes.c_double(vs), (ctypes.c_double * 3)(*lo), *shape)
 
 
 # ------------------------------------------------------------------------------------------------------ voxelization
@@ -146,43 +111,37 @@ def voxelize_stages(vertices, faces, voxel_size, min_bound, max_bound, return_oc
         return _empty_grid(vs, lo, shape, dev, return_occupancy)
     if nv == 0:
         raise ValueError("voxelize_mesh: faces given without vertices")
-    c = _Call(vs, lo, shape, dev)
-    L = c.L
-    ws = _Workspace(dev)
+    grid = _grid_args(vs, lo, shape)
+    ws = Workspace(dev)                 # one for all stages, released when the grid is returned
+    run = lambda name, *args, workspace=False, error="bad argument": call(
+        name, dev, *args, workspace=workspace, what="voxelize_mesh", errors={-2: "{what}: " + error})
     ints = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        st = _C._stream(dev)
         mark("plan")
         tri_box, col_start = ints(nf * 6), ints(nf + 1)
         num_items = ctypes.c_int(0)
-        rc = L.gsr_voxel_plan(ws.fn, None, _C._ptr(v), ctypes.c_int(nv), _C._ptr(f), ctypes.c_int(nf), *c.grid(), _C._ptr(tri_box),
-                              _C._ptr(col_start), ctypes.byref(num_items), st)
-        _rc("voxelize_mesh", rc, "a face index lies outside [0, V), a vertex coordinate is not finite, or the mesh covers more "
-                                 "than 2^30 voxel columns")
+        run("gsr_voxel_plan", v, nv, f, nf, *grid, tri_box, col_start, ctypes.byref(num_items), workspace=ws,
+            error="a face index lies outside [0, V), a vertex coordinate is not finite, or the mesh covers more than 2^30 voxel columns")
         mark("count")
         item_start = ints(num_items.value + 1)
         num_pairs = ctypes.c_int(0)
-        rc = L.gsr_voxel_count(ws.fn, None, _C._ptr(v), _C._ptr(f), ctypes.c_int(nf), *c.grid(), _C._ptr(tri_box), _C._ptr(col_start),
-                               num_items, ctypes.c_void_p(item_start.data_ptr()), ctypes.byref(num_pairs), st)
-        _rc("voxelize_mesh", rc, "more than 2^30 (voxel, triangle) pairs")
+        run("gsr_voxel_count", v, f, nf, *grid, tri_box, col_start, num_items, item_start, ctypes.byref(num_pairs), workspace=ws,
+            error="more than 2^30 (voxel, triangle) pairs")
         npairs = num_pairs.value
         if npairs == 0:
             mark("done")
             return _empty_grid(vs, lo, shape, dev, return_occupancy)
         mark("emit")
         pair_voxel, pair_tri_in = ints(npairs), ints(npairs)
-        rc = L.gsr_voxel_emit(_C._ptr(v), _C._ptr(f), ctypes.c_int(nf), *c.grid(), _C._ptr(tri_box), _C._ptr(col_start), num_items,
-                              _C._ptr(item_start), _C._ptr(pair_voxel), _C._ptr(pair_tri_in), st)
-        _rc("voxelize_mesh", rc, "bad argument")
+        run("gsr_voxel_emit", v, f, nf, *grid, tri_box, col_start, num_items, item_start, pair_voxel, pair_tri_in)
         mark("sort")
         voxel_index, pair_start, pair_tri = ints(npairs), ints(npairs + 1), ints(npairs)
         grid_index = torch.empty((npairs, 3), dtype=torch.int32, device=dev)
         nn = shape[0] * shape[1] * shape[2]
         occ = ints((nn + 31) // 32) if return_occupancy else None
         num_voxels = ctypes.c_int(0)
-        rc = L.gsr_voxel_sort(ws.fn, None, _C._ptr(pair_voxel), _C._ptr(pair_tri_in), num_pairs, *c.n, _C._ptr(voxel_index),
-                              _C._ptr(pair_start), _C._ptr(pair_tri), _C._ptr(grid_index), _C._ptr(occ), ctypes.byref(num_voxels), st)
-        _rc("voxelize_mesh", rc, "bad argument")
+        run("gsr_voxel_sort", pair_voxel, pair_tri_in, num_pairs, *shape, voxel_index, pair_start, pair_tri, grid_index, occ,
+            ctypes.byref(num_voxels), workspace=ws)
         mark("done")
     nvox = num_voxels.value
     return VoxelGrid(grid_index[:nvox].clone(), voxel_index[:nvox].clone(), pair_start[:nvox + 1].clone(), pair_tri, shape, vs, lo, occ)
@@ -206,8 +165,7 @@ def closest_on_mesh(grid, vertices, faces, vertex_colors=None):
     if not isinstance(grid, VoxelGrid):
         raise TypeError(f"grid must be a VoxelGrid, got {type(grid).__name__}")
     dev = _mesh(vertices, faces, vertex_colors)
-    if grid.voxel_index.device != dev:
-        raise ValueError(f"grid is on {grid.voxel_index.device}, vertices on {dev}")
+    same_device(dev, ref="vertices", grid=grid.voxel_index)
     v = vertices.detach().to(torch.float64).contiguous()
     f = faces.detach().to(torch.int32).contiguous()
     col = None if vertex_colors is None else vertex_colors.detach().contiguous()
@@ -215,12 +173,9 @@ def closest_on_mesh(grid, vertices, faces, vertex_colors=None):
     tri = torch.empty(nvox, dtype=torch.int32, device=dev)
     uvw = torch.empty((nvox, 3), dtype=torch.float64, device=dev)
     color = None if col is None else torch.empty((nvox, 3), dtype=torch.float32, device=dev)
-    c = _Call(grid.voxel_size, grid.origin, grid.shape, dev)
-    with torch.cuda.device(dev):
-        rc = c.L.gsr_voxel_closest(_C._ptr(v), ctypes.c_int(v.shape[0]), _C._ptr(f), ctypes.c_int(f.shape[0]), _C._ptr(col), *c.grid(),
-                                   _C._ptr(grid.voxel_index), _C._ptr(grid.pair_start), _C._ptr(grid.pair_tri), ctypes.c_int(nvox),
-                                   _C._ptr(tri), _C._ptr(uvw), _C._ptr(color), _C._stream(dev))
-    _rc("closest_on_mesh", rc, "bad argument")
+    call("gsr_voxel_closest", dev, v, v.shape[0], f, f.shape[0], col, *_grid_args(grid.voxel_size, grid.origin, grid.shape),
+         grid.voxel_index, grid.pair_start, grid.pair_tri, nvox, tri, uvw, color, what="closest_on_mesh",
+         errors={-2: "{what}: bad argument"})
     out = dict(closest_tri=tri, closest_uvw=uvw)
     if color is not None:
         out["color"] = color
@@ -237,8 +192,7 @@ def normalize_mesh(vertices):
         raise TypeError(f"vertices must be float32, got {vertices.dtype}")
     if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1:
         raise ValueError(f"vertices must have shape [V, 3] with V >= 1, got {list(vertices.shape)}")
-    if vertices.device.type != "cuda":
-        raise ValueError(f"vertices is on '{vertices.device}': gaustudio_amd runs on ROCm devices only (no CPU fallback)")
+    on_rocm(ValueError, vertices=vertices)
     v = vertices.detach().to(torch.float64)
     lo, hi = v.min(dim=0).values, v.max(dim=0).values
     center = (lo + hi) / 2

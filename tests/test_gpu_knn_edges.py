@@ -133,8 +133,8 @@ def test_knn_rejects_non_finite_queries(value, row, col, nq):
 def test_knn_error_codes_are_told_apart():
     """The C entry: an invalid argument, a non-finite point and a non-finite query have return codes of their own, and
     the wrapper says "not finite" for the last two only."""
-    from gaustudio_amd import _C, pcd_fusion
-    ws = pcd_fusion._Workspace(DEV)
+    from gaustudio_amd import _C, _abi, pcd_fusion
+    ws = _abi.Workspace(DEV)
     p = dev(edge.cloud("n65"))
     q = p[:5].clone()
     d2 = torch.empty(65 * 4, dtype=torch.float64, device=DEV)
@@ -158,7 +158,7 @@ def test_knn_error_codes_are_told_apart():
     assert call(p, 65, q, 5, 4) == -6                        # GSR_ERR_NONFINITE_QUERY
     assert call(p, 65, q, 4, 4) == 0                         # the fifth query is not read
     with pytest.raises(RuntimeError, match=r"rc=-2") as e:
-        pcd_fusion._rc("knn", -2)
+        _abi.raise_status(-2, "knn", pcd_fusion._ERRORS)
     assert "finite" not in str(e.value)
 
 

@@ -225,7 +225,7 @@ def test_pair_sort_past_one_radix_tile_on_one_and_two_digit_grids(n2):
 # ---------------------------------------------------------------------------------------------- 9. errors
 def test_errors_leave_the_outputs_untouched():
     from gaustudio_amd import _C, voxelize as vx
-    from gaustudio_amd.pcd_fusion import _Workspace
+    from gaustudio_amd._abi import Workspace
     t = _torch()
     v, f = mm.icosphere(1)
     vn, _, _ = mm.normalize_mesh(v)
@@ -246,7 +246,7 @@ def test_errors_leave_the_outputs_untouched():
         tri_box = t.full((nf * 6,), -77, dtype=t.int32, device="cuda")
         col_start = t.full((nf + 1,), -77, dtype=t.int32, device="cuda")
         items = ctypes.c_int(-77)
-        ws = _Workspace(vd.device)
+        ws = Workspace(vd.device)
         rc = _C.lib().gsr_voxel_plan(ws.fn, None, _C._ptr(vd), ctypes.c_int(vv.shape[0]), _C._ptr(fd), ctypes.c_int(nf),
                                      ctypes.c_double(1 / 16), (ctypes.c_double * 3)(*MB), ctypes.c_int(16), ctypes.c_int(16),
                                      ctypes.c_int(16), _C._ptr(tri_box), _C._ptr(col_start), ctypes.byref(items), _C._stream(vd.device))

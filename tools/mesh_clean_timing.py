@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "examples"))
 import mesh_clean_model as cm  # noqa: E402
 import mesh_raster_model as mm  # noqa: E402
 from gaustudio_amd import GaussianRasterizationSettings, GaussianRasterizer, _C, formats, mesh_clean, postprocess as pp  # noqa: E402
-from gaustudio_amd.mesh_raster import _Workspace  # noqa: E402
+from gaustudio_amd._abi import Workspace  # noqa: E402
 from gaustudio_amd.tsdf import TSDFVolume  # noqa: E402
 
 DEV = torch.device("cuda", 0)
@@ -94,7 +94,7 @@ def measure(name, verts, faces, repeat):
     st = _C._stream(DEV)
 
     def cluster():
-        ws = _Workspace(DEV)
+        ws = Workspace(DEV)
         return L.gsr_mesh_cluster_triangles(ws.fn, None, _C._ptr(faces), ctypes.c_int(F), ctypes.c_int(V), _C._ptr(clusters),
                                             _C._ptr(counts), ctypes.byref(rounds), st)
     C = cluster()
@@ -102,7 +102,7 @@ def measure(name, verts, faces, repeat):
     area = torch.empty(C, dtype=torch.float64, device=DEV)
 
     def areas():
-        ws = _Workspace(DEV)
+        ws = Workspace(DEV)
         assert L.gsr_mesh_cluster_area(ws.fn, None, _C._ptr(verts), ctypes.c_int(V), _C._ptr(faces), ctypes.c_int(F),
                                        _C._ptr(clusters), ctypes.c_int(C), _C._ptr(area), st) == 0
     remove = ~mesh_clean.keep_clusters(counts[:C], 0.5)[clusters.long()]

@@ -1,6 +1,7 @@
 // gsr_psr.hip -- Shape-as-Points meshing (gs-extract-pcd --meshing sap) on the device: the differentiable Poisson solver DPSR
-// of gaustudio/utils/graphics_utils.py:19-333 (forward only) and a dense indexed marching cubes in place of the reference's
-// CPU round trip through skimage.  The two FFTs between the stages stay with torch.fft (gaustudio_amd/sap.py).
+// of gaustudio/utils/graphics_utils.py:19-333, forward and backward, and a dense indexed marching cubes with vertex normals
+// in place of the reference's CPU round trip through skimage.  The two FFTs between the stages stay with torch.fft, which
+// differentiates them itself (gaustudio_amd/sap.py).
 //
 // Contract:
 //   * index and weight arithmetic of a point is the reference's fp32 chain, operation for operation (axis_of below);
@@ -19,7 +20,11 @@
 //   * spectral, normalize: pure HBM streams, grid-stride loops, 8 / 16 bytes per lane, no LDS.
 //   * interp: one lane per point (8 scattered loads), block partial sums in a fixed LDS tree, one block adds the partials.
 //   * marching cubes: classify (case + owned-edge flags per node, computed from the node's own neighbours: no atomics) ->
-//     two int scans -> emit vertices, emit triangles.
+//     two int scans -> emit vertices, emit triangles, emit vertex normals (the same walk as the vertices).
+//   * backward: the backward of a scatter is a gather and that of a gather a scatter.
+//     rasterize_bwd and interp_bwd are gathers, one lane per point over its 8 corners; the grid gradient of interp IS the
+//     forward scatter (gsr_psr_rasterize with one channel), so there is no second scatter.  spectral_bwd and normalize_bwd
+//     are streams like their forwards; normalize_bwd also leaves block partials that one block adds into grad_mean.
 // Plain HIP C++.  No float atomics, no inline assembly; the only atomics are integer vector atomics (cell histogram, status
 // word, the LDS histogram of the radix sort).
 #include <hip/hip_runtime.h>
@@ -361,6 +366,220 @@ __global__ void __launch_bounds__(256) psr_mc_triangles(int r0, int r1, int r2, 
 	}
 }
 
+// The edge end's central difference along one axis (spacing 1, index units); one-sided on the two faces of the grid
+__device__ __forceinline__ float psr_node_diff(const float* __restrict__ g, long long lin, int idx, int r, long long st)
+{
+	if (idx == 0) return g[lin + st] - g[lin];
+	if (idx == r - 1) return g[lin] - g[lin - st];
+	return (g[lin + st] - g[lin - st]) * 0.5f;
+}
+
+// Vertex normals in the order of psr_mc_vertices: the grid's gradient at the two ends of the crossing edge, interpolated with
+// the vertex's own t (fp32, ga + t * (gb - ga)), divided by max(|n|, 1e-6).
+__global__ void __launch_bounds__(256) psr_mc_normals(const float* __restrict__ g, int r0, int r1, int r2, float level,
+                                                      const uint32_t* __restrict__ info, const int* __restrict__ voff,
+                                                      float* __restrict__ normals)
+{
+	const long long nn = (long long)r0 * r1 * r2;
+	const long long lin = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (lin >= nn) return;
+	const uint32_t fl = info[lin] >> 8;
+	if (!fl) return;
+	const int idx[3] = {(int)(lin / ((long long)r2 * r1)), (int)((lin / r2) % r1), (int)(lin % r2)};
+	const int r[3] = {r0, r1, r2};
+	const long long st[3] = {(long long)r1 * r2, r2, 1};
+	const float a0 = g[lin];
+	float ga[3];
+	for (int d = 0; d < 3; d++) ga[d] = psr_node_diff(g, lin, idx[d], r[d], st[d]);
+	size_t v = (size_t)voff[lin];
+	for (int a = 0; a < 3; a++) {
+		if (!((fl >> a) & 1)) continue;
+		const long long lb = lin + st[a];      // the edge flag says idx[a] + 1 < r[a]
+		const float t = (level - a0) / (g[lb] - a0);
+		float n[3];
+		for (int d = 0; d < 3; d++) {
+			const float gb = psr_node_diff(g, lb, idx[d] + (d == a ? 1 : 0), r[d], st[d]);
+			n[d] = ga[d] + t * (gb - ga[d]);
+		}
+		const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+		const float den = len > 1e-6f ? len : 1e-6f;
+		normals[3 * v] = n[0] / den; normals[3 * v + 1] = n[1] / den; normals[3 * v + 2] = n[2] / den;
+		v++;
+	}
+}
+
+// ------------------------------------------------------------------------------------------------------ backward
+// What torch autograd gives the reference for one axis: a factor |p - pos| / cs differentiates to sign(p - pos) / cs with
+// sign(0) = 0; floor and ceil contribute nothing.  d0 goes with node i0 (pos = x1), d1 with node i1 (pos = x0).
+struct AxisD { float d0, d1; };
+__device__ __forceinline__ float psr_sign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+__device__ __forceinline__ AxisD axis_deriv(float p, float cs)
+{
+	AxisD a;
+	const float f0 = floorf(p / cs);
+	const float x0 = f0 * cs, x1 = (f0 + 1.0f) * cs;
+	a.d0 = psr_sign(p - x1) / cs;
+	a.d1 = psr_sign(p - x0) / cs;
+	return a;
+}
+
+// One lane per point, the 8 corners in the order of psr_interp (k0 slowest).  g' = g[c, node] (/ (float)max(cnt, 1) when
+// weighted), all fp32: grad_values[n, c] = sum_k (double)(w_k g'), grad_points[n, d] = sum_c sum_k (double)((dw_kd g') v_c),
+// dw_kd the corner weight with the factor of axis d replaced by its derivative.  Each sum in fp64, rounded once.
+__global__ void __launch_bounds__(256) psr_rasterize_bwd(const float* __restrict__ gg, const float* __restrict__ pts,
+                                                         const float* __restrict__ vals, int n, int C, Res R, int weighted,
+                                                         const int* __restrict__ counts, float* __restrict__ gvals,
+                                                         float* __restrict__ gpts, int* status)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const float x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+	if (!(axis_ok(x, R.cs[0], R.r[0]) && axis_ok(y, R.cs[1], R.r[1]) && axis_ok(z, R.cs[2], R.r[2]))) {
+		atomicOr(status, 1);
+		return;
+	}
+	const size_t nn = (size_t)R.r[0] * R.r[1] * R.r[2];
+	const Axis ax = axis_of(x, R.cs[0], R.rf[0]), ay = axis_of(y, R.cs[1], R.rf[1]), az = axis_of(z, R.cs[2], R.rf[2]);
+	const AxisD dx = axis_deriv(x, R.cs[0]), dy = axis_deriv(y, R.cs[1]), dz = axis_deriv(z, R.cs[2]);
+	float v[GSR_PSR_MAX_CHANNELS] = {0.f, 0.f, 0.f, 0.f};
+	for (int c = 0; c < GSR_PSR_MAX_CHANNELS; c++)
+		if (c < C) v[c] = vals[(size_t)C * i + c];
+	double av[GSR_PSR_MAX_CHANNELS] = {0.0, 0.0, 0.0, 0.0};
+	double ap[3] = {0.0, 0.0, 0.0};
+	for (int c = 0; c < GSR_PSR_MAX_CHANNELS; c++) {
+		if (c >= C) break;
+		for (int k = 0; k < 8; k++) {
+			const int k0 = k >> 2, k1 = (k >> 1) & 1, k2 = k & 1;
+			const size_t node = ((size_t)(k0 ? ax.i1 : ax.i0) * R.r[1] + (k1 ? ay.i1 : ay.i0)) * R.r[2] + (k2 ? az.i1 : az.i0);
+			float g = gg[c * nn + node];
+			if (weighted) {
+				const int cnt = counts[node];
+				g = g / (float)(cnt == 0 ? 1 : cnt);
+			}
+			const float wx = k0 ? ax.w1 : ax.w0, wy = k1 ? ay.w1 : ay.w0, wz = k2 ? az.w1 : az.w0;
+			const float sx = k0 ? dx.d1 : dx.d0, sy = k1 ? dy.d1 : dy.d0, sz = k2 ? dz.d1 : dz.d0;
+			av[c] += (double)(((wx * wy) * wz) * g);
+			ap[0] += (double)((((sx * wy) * wz) * g) * v[c]);
+			ap[1] += (double)((((wx * sy) * wz) * g) * v[c]);
+			ap[2] += (double)((((wx * wy) * sz) * g) * v[c]);
+		}
+	}
+	if (gvals)
+		for (int c = 0; c < GSR_PSR_MAX_CHANNELS; c++)
+			if (c < C) gvals[(size_t)C * i + c] = (float)av[c];
+	if (gpts)
+		for (int d = 0; d < 3; d++) gpts[3 * (size_t)i + d] = (float)ap[d];
+}
+
+// grad_points[n, d] = sum_k (double)((grid[node_k] dw_kd) grad_out[n]), fp64, rounded once
+__global__ void __launch_bounds__(256) psr_interp_bwd(const float* __restrict__ grid, Res R, const float* __restrict__ pts, int n,
+                                                      const float* __restrict__ gout, float* __restrict__ gpts, int* status)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const float x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+	if (!(axis_ok(x, R.cs[0], R.r[0]) && axis_ok(y, R.cs[1], R.r[1]) && axis_ok(z, R.cs[2], R.r[2]))) {
+		atomicOr(status, 1);
+		return;
+	}
+	const Axis ax = axis_of(x, R.cs[0], R.rf[0]), ay = axis_of(y, R.cs[1], R.rf[1]), az = axis_of(z, R.cs[2], R.rf[2]);
+	const AxisD dx = axis_deriv(x, R.cs[0]), dy = axis_deriv(y, R.cs[1]), dz = axis_deriv(z, R.cs[2]);
+	const float go = gout[i];
+	double ap[3] = {0.0, 0.0, 0.0};
+	for (int k = 0; k < 8; k++) {
+		const int k0 = k >> 2, k1 = (k >> 1) & 1, k2 = k & 1;
+		const size_t node = ((size_t)(k0 ? ax.i1 : ax.i0) * R.r[1] + (k1 ? ay.i1 : ay.i0)) * R.r[2] + (k2 ? az.i1 : az.i0);
+		const float lat = grid[node];
+		const float wx = k0 ? ax.w1 : ax.w0, wy = k1 ? ay.w1 : ay.w0, wz = k2 ? az.w1 : az.w0;
+		const float sx = k0 ? dx.d1 : dx.d0, sy = k1 ? dy.d1 : dy.d0, sz = k2 ? dz.d1 : dz.d0;
+		ap[0] += (double)((lat * ((sx * wy) * wz)) * go);
+		ap[1] += (double)((lat * ((wx * sy) * wz)) * go);
+		ap[2] += (double)((lat * ((wx * wy) * sz)) * go);
+	}
+	for (int d = 0; d < 3; d++) gpts[3 * (size_t)i + d] = (float)ap[d];
+}
+
+// The adjoint of psr_spectral in PyTorch's convention for complex gradients: grad_N_d = conj(c_d) grad_Phi with
+// c_d = -i w_d G / (Lap + 1e-6), i.e. (w_d G / den) (-Im, Re) of grad_Phi; element 0 (Phi[0,0,0] = 0) gets nothing.
+// fp32 chain: a = grad_Phi / den, then (-a.y w_d, a.x w_d), then times G (fp64 filter, cast, as in the forward).
+__global__ void __launch_bounds__(256) psr_spectral_bwd(const float2* __restrict__ gphi, int r0, int r1, int r2h, double sig,
+                                                        float2* __restrict__ gspec)
+{
+	const long long ne = (long long)r0 * r1 * r2h;
+	const float pi = (float)M_PI;
+	for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < ne; e += (long long)gridDim.x * 256) {
+		const int k = (int)(e % r2h), j = (int)((e / r2h) % r1), i = (int)(e / ((long long)r2h * r1));
+		const int f[3] = {fft_freq(i, r0), fft_freq(j, r1), k};
+		const double dis = sqrt((double)f[0] * f[0] + (double)f[1] * f[1] + (double)f[2] * f[2]);
+		const double t = (sig * 2.0) * dis / (double)r0;
+		const float g = (float)exp(-0.5 * (t * t));
+		float om[3], lap = 0.f;
+		for (int d = 0; d < 3; d++) {
+			om[d] = ((float)f[d] * 2.0f) * pi;
+			const float o2 = om[d] * om[d];
+			lap = d == 0 ? o2 : lap + o2;
+		}
+		const float den = (-lap) + 1e-6f;
+		const float2 gp = gphi[e];
+		const float ar = gp.x / den, ai = gp.y / den;
+		for (int d = 0; d < 3; d++) {
+			float2 o;
+			o.x = ((-ai) * om[d]) * g;
+			o.y = (ar * om[d]) * g;
+			if (e == 0) { o.x = 0.f; o.y = 0.f; }
+			gspec[(size_t)d * ne + e] = o;
+		}
+	}
+}
+
+__device__ __forceinline__ float psr_norm_bwd_one(float go, float o, float a, int scale, int do_tanh)
+{
+	if (do_tanh) go = go * (1.0f - o * o);
+	if (scale) go = (-go) / a * 0.5f;
+	return go;
+}
+// grad_in = grad_out (1 - out^2) [tanh] (-0.5 / |v0|) [scale], |v0| = params[1] a constant; every lane adds its own values
+// in fp64 in loop order, a block its lanes in the fixed tree: partial[blockIdx.x]
+__global__ void __launch_bounds__(256) psr_normalize_bwd(const float* gout, const float* out, float* gin, long long n, long long nvec,
+                                                         const float* __restrict__ params, int scale, int do_tanh,
+                                                         double* __restrict__ partial)
+{
+	__shared__ double red[256];
+	const float a = params[1];
+	const long long t0 = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+	const float4* go4 = reinterpret_cast<const float4*>(gout);
+	const float4* o4 = reinterpret_cast<const float4*>(out);
+	float4* gi4 = reinterpret_cast<float4*>(gin);
+	double acc = 0.0;
+	for (long long i = t0; i < nvec; i += step) {
+		float4 v = go4[i];
+		const float4 o = do_tanh ? o4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+		v.x = psr_norm_bwd_one(v.x, o.x, a, scale, do_tanh);
+		v.y = psr_norm_bwd_one(v.y, o.y, a, scale, do_tanh);
+		v.z = psr_norm_bwd_one(v.z, o.z, a, scale, do_tanh);
+		v.w = psr_norm_bwd_one(v.w, o.w, a, scale, do_tanh);
+		gi4[i] = v;
+		acc += (double)v.x; acc += (double)v.y; acc += (double)v.z; acc += (double)v.w;
+	}
+	for (long long i = 4 * nvec + t0; i < n; i += step) {
+		const float v = psr_norm_bwd_one(gout[i], do_tanh ? out[i] : 0.f, a, scale, do_tanh);
+		gin[i] = v;
+		acc += (double)v;
+	}
+	const double s = block_sum_256(acc, red);
+	if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// grad_mean[0] = -(sum of the block partials in a fixed order): the shift subtracts the mean from every value
+__global__ void __launch_bounds__(256) psr_neg_sum(const double* __restrict__ partial, int np, double* __restrict__ gmean)
+{
+	__shared__ double red[256];
+	double s = 0.0;
+	for (int b = threadIdx.x; b < np; b += 256) s += partial[b];
+	const double t = block_sum_256(s, red);
+	if (threadIdx.x == 0) gmean[0] = -t;
+}
+
 }  // namespace
 
 extern "C" {
@@ -481,6 +700,79 @@ int gsr_psr_mc_emit(const float* grid, int r0, int r1, int r2, float level, cons
 	const long long nn = (long long)r0 * r1 * r2;
 	if (vertices) hipLaunchKernelGGL(psr_mc_vertices, dim3(blocks(nn)), dim3(256), 0, s, grid, r0, r1, r2, level, node_info, vertex_offset, vertices);
 	if (faces) hipLaunchKernelGGL(psr_mc_triangles, dim3(blocks(nn)), dim3(256), 0, s, r0, r1, r2, node_info, vertex_offset, triangle_offset, faces);
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_psr_mc_normals(const float* grid, int r0, int r1, int r2, float level, const uint32_t* node_info, const int* vertex_offset,
+                       float* normals, void* stream)
+{
+	if (!grid || !good_res(r0, r1, r2) || !node_info || !vertex_offset || !normals) return GSR_ERR_ARG;
+	const long long nn = (long long)r0 * r1 * r2;
+	hipLaunchKernelGGL(psr_mc_normals, dim3(blocks(nn)), dim3(256), 0, (hipStream_t)stream, grid, r0, r1, r2, level, node_info,
+	                   vertex_offset, normals);
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_psr_rasterize_bwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grad_grid, const float* points,
+                          int num_points, const float* values, int channels, int r0, int r1, int r2, int weighted,
+                          const int* counts, float* grad_values, float* grad_points, void* stream)
+{
+	if (!grad_grid || !good_res(r0, r1, r2) || channels < 1 || channels > GSR_PSR_MAX_CHANNELS || num_points < 0 ||
+	    num_points > (1 << 28) || (num_points > 0 && (!points || !values)) || (weighted && !counts))
+		return GSR_ERR_ARG;
+	if (num_points == 0 || (!grad_values && !grad_points)) return GSR_OK;
+	hipStream_t s = (hipStream_t)stream;
+	int* status;
+	auto carve = [&](Arena& ws) { status = ws.take<int>(1); };
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, 4, s));
+	hipLaunchKernelGGL(psr_rasterize_bwd, dim3(blocks(num_points)), dim3(256), 0, s, grad_grid, points, values, num_points, channels,
+	                   make_res(r0, r1, r2), weighted, counts, grad_values, grad_points, status);
+	const int rc = read_status(status, s);
+	if (rc) return rc;
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_psr_interp_bwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grid, int r0, int r1, int r2,
+                       const float* points, int num_points, const float* grad_samples, float* grad_points, void* stream)
+{
+	if (!grid || !good_res(r0, r1, r2) || !points || num_points < 1 || !grad_samples || !grad_points) return GSR_ERR_ARG;
+	hipStream_t s = (hipStream_t)stream;
+	int* status;
+	auto carve = [&](Arena& ws) { status = ws.take<int>(1); };
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	GSR_TRY(hipMemsetAsync(status, 0, 4, s));
+	hipLaunchKernelGGL(psr_interp_bwd, dim3(blocks(num_points)), dim3(256), 0, s, grid, make_res(r0, r1, r2), points, num_points,
+	                   grad_samples, grad_points, status);
+	const int rc = read_status(status, s);
+	if (rc) return rc;
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_psr_spectral_bwd(const float* grad_phi, int r0, int r1, int r2, double sig, float* grad_spectrum, void* stream)
+{
+	if (!grad_phi || !grad_spectrum || !good_res(r0, r1, r2)) return GSR_ERR_ARG;
+	const long long ne = (long long)r0 * r1 * (r2 / 2 + 1);
+	hipLaunchKernelGGL(psr_spectral_bwd, dim3(stream_blocks(ne)), dim3(256), 0, (hipStream_t)stream,
+	                   reinterpret_cast<const float2*>(grad_phi), r0, r1, r2 / 2 + 1, sig, reinterpret_cast<float2*>(grad_spectrum));
+	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_psr_normalize_bwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grad_out, const float* grid_out,
+                          long long count, const float* params, int scale, int apply_tanh, float* grad_in, double* grad_mean,
+                          void* stream)
+{
+	if (!grad_out || !grad_in || count < 1 || !params || (apply_tanh && !grid_out)) return GSR_ERR_ARG;
+	hipStream_t s = (hipStream_t)stream;
+	const unsigned nb = stream_blocks(count / 4 + 1);
+	double *partial, *m;
+	auto carve = [&](Arena& ws) { partial = ws.take<double>(nb); m = ws.take<double>(1); };
+	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
+	const bool aligned = (((uintptr_t)grad_out | (uintptr_t)grad_in | (uintptr_t)grid_out) & 15) == 0;
+	const long long nvec = aligned ? count / 4 : 0;
+	hipLaunchKernelGGL(psr_normalize_bwd, dim3(nb), dim3(256), 0, s, grad_out, grid_out, grad_in, count, nvec, params, scale,
+	                   apply_tanh, partial);
+	hipLaunchKernelGGL(psr_neg_sum, dim3(1), dim3(256), 0, s, partial, (int)nb, grad_mean ? grad_mean : m);
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
 

@@ -655,7 +655,7 @@ int gsr_mesh_compact(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const fl
  * grid_interp and its normalisation; a dense marching cubes in place of the CPU round trip through skimage).  Additive to
  * ABI 6, in the style of gsr_knn / gsr_mesh_*: inputs and outputs are caller-owned device memory, scratch comes from the
  * gsr_alloc_fn callback (called once per call), `stream` is the HIP stream of every launch; the entries that say so read a
- * flag or two counts back and wait on `stream` once.  Forward only.  Deterministic: no float atomics, bit-identical from run
+ * flag or two counts back and wait on `stream` once.  The backward entries follow below.  Deterministic: no float atomics, bit-identical from run
  * to run.  Grids are dense, row-major [r0, r1, r2] f32 with every size >= 2 and r0 r1 r2 < 2^30.  The two FFTs between the
  * stages are the caller's.  Contract: INTEGRATION.md s17; design: gsr_psr.hip, DESIGN.md s14. ---- */
 #define GSR_PSR_MAX_CHANNELS 4
@@ -703,6 +703,45 @@ int gsr_psr_mc_classify(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const
                         void* stream);
 int gsr_psr_mc_emit(const float* grid, int r0, int r1, int r2, float level, const uint32_t* node_info, const int* vertex_offset,
                     const int* triangle_offset, float* vertices, int* faces, void* stream);
+
+/* Vertex normals of the mesh of gsr_psr_mc_emit, from the node_info / vertex_offset of gsr_psr_mc_classify on the same grid and
+ * level: normals[num_vertices,3] f32 in vertex order.  Per vertex the grid's gradient at the two end nodes of its edge
+ * (central difference (g[i+1] - g[i-1]) * 0.5 per axis in index units, one-sided g[1] - g[0] / g[r-1] - g[r-2] on the faces
+ * of the grid), n = ga + t (gb - ga) with the vertex's own t = (level - a) / (b - a), then n / max(|n|, 1e-6); all fp32. */
+int gsr_psr_mc_normals(const float* grid, int r0, int r1, int r2, float level, const uint32_t* node_info, const int* vertex_offset,
+                       float* normals, void* stream);
+
+/* ---- The backward of the Shape-as-Points stages.  Additive to ABI 6.  The numeric contract is the
+ * forward's: the fp32 index / weight chain, fp32 terms added in fp64 in a fixed order and rounded once, no float atomics,
+ * bit-identical from run to run, GSR_ERR_ARG for a coordinate that is not finite or outside [0, 1).  Derivative rule: a
+ * weight factor |p - pos| / cubesize differentiates to sign(p - pos) / cubesize (fp32) with sign(0) = 0; floor, ceil and
+ * the pair counts contribute nothing.  dw_kd below is the weight of corner k with the factor of axis d so replaced. ---- */
+
+/* Backward of gsr_psr_rasterize, one lane per point: grad_grid[channels,r0,r1,r2], counts[r0,r1,r2] = the forward's counts
+ * (read only when weighted; g' = g / (float)max(count, 1), else g' = g).  grad_values[n,c] = sum_k (w_k g'[c,node_k]),
+ * grad_points[n,d] = sum_c sum_k ((dw_kd g'[c,node_k]) values[n,c]); corners k = (k0,k1,k2), k0 slowest.  Either output may
+ * be NULL.  Waits on `stream` once. */
+int gsr_psr_rasterize_bwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grad_grid, const float* points,
+                          int num_points, const float* values, int channels, int r0, int r1, int r2, int weighted,
+                          const int* counts, float* grad_values, float* grad_points, void* stream);
+
+/* Backward of gsr_psr_interp towards the points: grad_points[n,d] = sum_k ((grid[node_k] dw_kd) grad_samples[n]).  The
+ * gradient towards the grid is the adjoint scatter gsr_psr_rasterize(points, grad_samples, channels = 1, weighted = 0).
+ * Waits on `stream` once. */
+int gsr_psr_interp_bwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grid, int r0, int r1, int r2,
+                       const float* points, int num_points, const float* grad_samples, float* grad_points, void* stream);
+
+/* Backward of gsr_psr_spectral in PyTorch's convention for complex gradients: grad_phi[r0,r1,r2/2+1] complex64 ->
+ * grad_spectrum[3,r0,r1,r2/2+1] complex64, grad_N_d = conj(c_d) grad_phi with c_d = -i w_d G / (Lap + 1e-6), zero at
+ * element 0.  fp32 chain: a = grad_phi / (Lap + 1e-6), (-Im a w_d, Re a w_d), times G (fp64, cast, as in the forward). */
+int gsr_psr_spectral_bwd(const float* grad_phi, int r0, int r1, int r2, double sig, float* grad_spectrum, void* stream);
+
+/* Backward of gsr_psr_normalize: grid_out = the forward's output (read only with apply_tanh), params = the forward's params
+ * (|v[0]| is a constant: the reference detaches it).  In fp32 grad_in = grad_out (1 - out^2) with apply_tanh, then
+ * -grad_in / |v[0]| * 0.5 with scale.  grad_mean[1] (f64, device, NULL = not wanted) = -(fixed-order fp64 sum of grad_in). */
+int gsr_psr_normalize_bwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* grad_out, const float* grid_out,
+                          long long count, const float* params, int scale, int apply_tanh, float* grad_in, double* grad_mean,
+                          void* stream);
 
 /* ---- visual hull (csrc/gsr_hull.hip): the `VisualHull` initializer's carve, gaustudio/pipelines/initializers/mask.py:38-71 ----
  * A camera of the carve: m = full_proj_transform as the reference stores it (row-vector convention, row-major [4][4]:

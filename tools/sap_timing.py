@@ -1,12 +1,15 @@
 #!/usr/bin/env python
 """Stage times of gaustudio_amd.sap on the GPU, next to a plain-torch composition of the same stages on the same GPU
 (index_add_ for the scatter, torch.fft, broadcast arithmetic for the spectral solve, advanced indexing for the gather;
-written for this comparison).  The torch side stops at the grid: torch has no marching cubes.
+written for this comparison).  The torch side stops at the grid: torch has no marching cubes.  The backward stages
+(`*_bwd`, `dpsr_fwd_bwd`, `psr2mesh_bwd`) are timed the same way, the torch side through torch autograd of that composition
+(the reference's formulation: index_add_ / advanced indexing and their autograd adjoints).
 
     python tools/sap_timing.py [--res 128 256] [--points 100000 1000000] [--repeats 20] [--out sap_timing_out]
 
 Every figure is the median over `repeats` of a host clock around work that ends in a device synchronise, after 3 warm-up
-calls of the same shape.  Prints one table per (res, N) and writes them to <out>/sap_timing.json."""
+calls of the same shape.  Prints one table per (res, N) and writes them to <out>/sap_timing.json (the run quoted in README
+is kept as profiles/sap_timing.json)."""
 import argparse
 import json
 import os
@@ -87,7 +90,34 @@ def torch_interp(grid, pts):
 
 def torch_normalize(phi, fv):
     phi = phi - fv.mean()
-    return torch.tanh(-phi / phi[0, 0, 0].abs() * 0.5)
+    return torch.tanh(-phi / phi[0, 0, 0].detach().abs() * 0.5)        # the reference detaches |v0|
+
+
+# ---- backward timing -------------------------------------------------------------------------------------------------
+def leaf(t):
+    return t.detach().clone().requires_grad_(True)
+
+
+def backward_ms(fn, inputs, repeats):
+    """median time of the backward of fn(*inputs) alone: the graph is built once and retained."""
+    leaves = [leaf(t) for t in inputs]
+    out = fn(*leaves)
+    g = torch.randn_like(out)
+    return timed(lambda: torch.autograd.grad(out, leaves, g, retain_graph=True), repeats)[0]
+
+
+def hip_step(dpsr, V, N, W):
+    p, v = leaf(V), leaf(N)
+    (dpsr(p, v, apply_tanh=True) * W).sum().backward()
+    return p.grad, v.grad
+
+
+def torch_step(V, N, R, W):
+    p, v = leaf(V), leaf(N)
+    res = (R, R, R)
+    ph = torch.fft.irfftn(torch_spectral(torch.fft.rfftn(torch_rasterize(p, v, R), dim=(1, 2, 3)), R, 2.0), s=res, dim=(0, 1, 2))
+    (torch_normalize(ph, torch_interp(ph, p)) * W).sum().backward()
+    return p.grad, v.grad
 
 
 def main():
@@ -102,6 +132,10 @@ def main():
     dev = torch.device("cuda", 0)
     os.makedirs(args.out, exist_ok=True)
     rows = []
+
+    def bwd(fn, *inputs):
+        return backward_ms(fn, inputs, args.repeats)
+
     for R in args.res:
         for n in args.points:
             V, N = cloud(n, dev)
@@ -124,10 +158,32 @@ def main():
             hip["dpsr_total"], _ = timed(lambda: dpsr(V, N, apply_tanh=True), args.repeats)
             tor["dpsr_total"], _ = timed(lambda: torch_normalize(*(lambda p: (p, torch_interp(p, V)))(torch.fft.irfftn(
                 torch_spectral(torch.fft.rfftn(torch_rasterize(V, N, R), dim=(1, 2, 3)), R, 2.0), s=res, dim=(0, 1, 2)))), args.repeats)
+            # ---- backward: each stage's backward alone (a retained graph), then the solver forward + backward
+            hip["rasterize_bwd"] = bwd(lambda p, v: sap.point_rasterize(p, v, res, weighted=False), V, N)
+            tor["rasterize_bwd"] = bwd(lambda p, v: torch_rasterize(p, v, R), V, N)
+            hip["spectral_bwd"] = bwd(lambda x: torch.view_as_real(sap.spectral_solve(x, res, 2.0)), spec)
+            tor["spectral_bwd"] = bwd(lambda x: torch.view_as_real(torch_spectral(x, R, 2.0)), spec)
+            hip["interp_bwd"] = bwd(lambda g, p: sap.grid_interp(g, p), phi, V)
+            tor["interp_bwd"] = bwd(lambda g, p: torch_interp(g, p), phi, V)
+            hip["normalize_bwd"] = bwd(lambda g, m: sap.normalize_grid(g, m, scale=True, apply_tanh=True), phi, mean)
+            tor["normalize_bwd"] = bwd(lambda g, f: torch_normalize(g, f), phi, tfv)
+            hip["psr2mesh_bwd"] = bwd(lambda g: sap.psr2mesh(g)[0], grid)
+            W = torch.randn(res, device=dev)
+
+            hip["dpsr_fwd_bwd"], (gp, gv) = timed(lambda: hip_step(dpsr, V, N, W), args.repeats)
+            tor["dpsr_fwd_bwd"], (tgp, tgv) = timed(lambda: torch_step(V, N, R, W), args.repeats)
+            # a coordinate exactly on a node (p * R an integer; a few per 10^5 float32 points when R is a power of two) is where
+            # the two formulations differ by design: |p - pos| has derivative sign(0) = 0 there, the composition's 1 - fr has -R
+            off_node = ((V * R) != (V * R).floor()).all(1)
+            grad_agree = dict(points=float((gp - tgp)[off_node].abs().max() / tgp.abs().max()),
+                              normals=float((gv - tgv).abs().max() / tgv.abs().max()), node_aligned_points=int((~off_node).sum()))
             agree = float((grid - tgrid).abs().max())
-            row = dict(res=R, points=n, hip_ms=hip, torch_ms=tor, vertices=len(v), faces=len(f), max_abs_grid_diff=agree)
+            row = dict(res=R, points=n, hip_ms=hip, torch_ms=tor, vertices=len(v), faces=len(f), max_abs_grid_diff=agree,
+                       max_rel_grad_diff=grad_agree)
             rows.append(row)
-            print(f"res {R}^3, N = {n}: {len(v)} vertices, {len(f)} faces; max |hip grid - torch grid| = {agree:.2e}")
+            print(f"res {R}^3, N = {n}: {len(v)} vertices, {len(f)} faces; max |hip grid - torch grid| = {agree:.2e}; "
+                  f"max relative gradient difference: points {grad_agree['points']:.2e} "
+                  f"(off the {grad_agree['node_aligned_points']} node-aligned points), normals {grad_agree['normals']:.2e}")
             for k in hip:
                 print(f"  {k:15s} hip {hip[k]:9.3f} ms   torch {tor[k]:9.3f} ms" if k in tor else f"  {k:15s} hip {hip[k]:9.3f} ms")
             with open(os.path.join(args.out, "sap_timing.json"), "w") as fjson:

@@ -508,6 +508,23 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) void composite_bwd_kernel(
 //   ids a round earlier still, by unmasked loads whose values nothing touches until they are staged; one wait before the flush
 //   (see "software-pipelined staging" in the kernel).  Until round 8 the source said so and the ISA did not: a repack of the
 //   loaded words and exec-masked loads put s_waitcnt vmcnt(0) right behind each of the round's loads.
+//   LDS budget of one walk step of a wave (headline instantiation <FLAGS=0,TSEL=0,FX=1,CONLY=0>; LDS-pipe cycles per wave instruction:
+//   reads b32 2, b64 2, read2_b32 4, b128 4 -- but a 12-BYTE read, ds_read_b96, 8: it runs at 96 B/clk where the 16-byte one runs at
+//   256 --, writes b32 4, b64 / write2_b32 6, b128 13; profiles/r09_composite_bwd_lds.txt has the ISA):
+//                                                    until round 8                          since round 9
+//     record part A (px, py, -a/2, -b)               ds_read_b128            4              ds_read_b128   4
+//     record part B                                  ds_read_b96 (.w unused) 8              ds_read_b128   4   (-c/2, opacity, depth, r)
+//     record part C                                  ds_read_b96 (r, g, b)   8              ds_read_b64    2   (g, b)
+//     slab (q, w)                                    ds_write_b64            6              unchanged      6
+//     plane turn  read2_b32 + read_b32 + write2_b32 + write_b32      4 + 2 + 6 + 4 = 16     unchanged     16
+//     per group of 4 steps: list word (b32), centre (b64), two slab reads (b128)  12 -> 3   unchanged      3
+//                                                                           about 45                 about 35
+//   The ten words a step needs were three parts of 16 B in the layout of GsRec, of which the compiler read 16 + 12 + 12; they are
+//   regrouped at staging (sA / sB / sC below) so that the step reads 16 + 16 + 8 (the exact modes 16 + 16 + 16: pcut rides in sC.z).
+//   Never read 12 bytes from LDS in a loop.  What is left is led by the plane turn (16 of 35).  The "one float4 per lane and turn"
+//   form above is NOT cheaper on this pipe (read b128 4 + write b128 13 = 17, and it spilled).  A cheaper form exists and is small:
+//   with the three sums of a lane in adjacent words of the slot (a permutation of the plane's ten words, undone by the flush; the
+//   additions and their order stay) a turn is read b64 + b32, write b64 + b32 = 2 + 2 + 6 + 4 = 14, two cycles of 35 less.  Not built.
 // A wave walks max over its quarters (C3: 0.73x the steps of the 8x8 walk), and phase 2 touches only hit quarters.
 // The median-depth gradient (one Gaussian per pixel, the list position the forward recorded) is added once per pixel,
 // by an LDS atomic before the walk of the batch that position falls into.
@@ -545,9 +562,10 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
     const float* __restrict__ dL_dpix_opacity, float* __restrict__ rows, uint8_t* __restrict__ row_flags,
     const GsCtl* __restrict__ ctl)
 {
-	__shared__ float4 sA[GSR_BWQ_BATCH + 1];   // q0: px, py, -a/2, -b        (last slot: the sentinel)
-	__shared__ float4 sB[GSR_BWQ_BATCH + 1];   // q1: -c/2, opacity, depth, pcut
-	__shared__ float4 sC[GSR_BWQ_BATCH + 1];   // q2: r, g, b, -
+	// the staged records, regrouped from the 16-B parts of GsRec so that a step reads 16 + 16 + 8 bytes (see "LDS budget" above)
+	__shared__ float4 sA[GSR_BWQ_BATCH + 1];   // px, py, -a/2, -b            (last slot: the sentinel, all zeros in all three)
+	__shared__ float4 sB[GSR_BWQ_BATCH + 1];   // -c/2, opacity, depth, r
+	__shared__ float4 sC[GSR_BWQ_BATCH + 1];   // g, b, pcut, 0 (spare)
 	__shared__ uint32_t s_row[GSR_BWQ_BATCH];
 	__shared__ uint16_t s_qmask[GSR_BWQ_BATCH];   // the forward's block masks of the staged instances (when it left them)
 	__shared__ __attribute__((aligned(16))) float s_plane[4][GSR_BWQ_BATCH * GSR_PLANE_STRIDE];
@@ -727,9 +745,14 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			const int sr = srec + 64 * h;
 			if (sr < cnt) {
 				if (spart == 0) sA[sr] = part[h];
-				else if (spart == 1) sB[sr] = part[h];
-				else if (spart == 2) {
-					sC[sr] = part[h];
+				else if (spart == 1) {   // q1 = {-c/2, opacity, depth, pcut}: three words of sB, pcut (and a zero in the spare word) to sC.zw
+					float* b = reinterpret_cast<float*>(&sB[sr]);
+					*reinterpret_cast<float2*>(b) = make_float2(part[h].x, part[h].y);
+					b[2] = part[h].z;
+					reinterpret_cast<float2*>(&sC[sr])[1] = make_float2(part[h].w, 0.f);
+				} else if (spart == 2) {   // q2 = {r, g, b, block mask word}: r to sB.w, (g, b) to sC -- words the part-1 thread does not write
+					reinterpret_cast<float*>(&sB[sr])[3] = part[h].x;
+					*reinterpret_cast<float2*>(&sC[sr]) = make_float2(part[h].y, part[h].z);
 					s_qmask[sr] = (uint16_t)(__float_as_uint(part[h].w) >> (16u * ((range.x + (uint32_t)(top - 1 - sr)) & 1u)));
 				} else {   // q3 = {rect min, rect max, clamp bits | dead corners, tiles}
 					const uint32_t q3x = __float_as_uint(part[h].x), q3y = __float_as_uint(part[h].y), q3z = __float_as_uint(part[h].z);
@@ -785,7 +808,9 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 					const uint32_t m16 = (uint32_t)s_qmask[jl] >> (8 * (wv >> 1) + 2 * (wv & 1));
 					mk = (m16 & 3u) | ((m16 >> 2) & 12u);
 				} else {
-					mk = gs_quarter_mask<2>(sA[jl], sB[jl], fbx, fby, 0xfu);
+					float4 q1 = sB[jl];    // the test wants q1 of the record: (-c/2, opacity, depth, pcut)
+					q1.w = sC[jl].z;
+					mk = gs_quarter_mask<2>(sA[jl], q1, fbx, fby, 0xfu);
 				}
 				const int pos = top - 1 - jl;
 				mk &= (pos < qm0 ? 1u : 0u) | (pos < qm1 ? 2u : 0u) | (pos < qm2 ? 4u : 0u) | (pos < qm3 ? 8u : 0u);
@@ -801,17 +826,26 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 		const int n = max(max(c0, c1), max(c2, c3));
 		const int my_cnt = qd == 0 ? c0 : qd == 1 ? c1 : qd == 2 ? c2 : c3;
 		// one list step of every quarter: (q, w) of the lane's pixel for the quarter's entry, into slab row `st`
-		struct Rec { float4 A, B; float3 C; };
+		// 16 + 16 + 8 bytes (FX; the exact modes need pcut: 16 + 16 + 16).  Never 12: a 96-bit LDS read costs two 128-bit ones
+		struct Rec { float4 A, B; float2 C; float pcut; };
 		auto fetch = [&](const uint32_t j) -> Rec {
 			Rec r;
 			r.A = *reinterpret_cast<const float4*>(recA + j * 16);
 			r.B = *reinterpret_cast<const float4*>(recB + j * 16);
-			r.C = *reinterpret_cast<const float3*>(recC + j * 16);
+			if (FX) {
+				r.C = *reinterpret_cast<const float2*>(recC + j * 16);
+				r.pcut = 0.f;
+			} else {
+				float4 c = *reinterpret_cast<const float4*>(recC + j * 16);
+				asm volatile("" : "+v"(c.w));   // the spare word counts as used: the compiler must not narrow the read to 12 bytes
+				r.C = make_float2(c.x, c.y);
+				r.pcut = c.z;
+			}
 			return r;
 		};
 		auto step = [&](const Rec& rc, const uint32_t j, const int st) {
 			const float4 A = rc.A, B = rc.B;
-			const float3 Cc = rc.C;
+			const float3 Cc = make_float3(B.w, rc.C.x, rc.C.y);   // r, g, b
 			const int pos = top - 1 - (int)j;   // == `contributor` after decrement (backward.cu:520)
 			const float dx = A.x - pixfx, dy = A.y - pixfy;
 			const float power = FMA(A.w * dx, dy, FMA(B.x * dy, dy, (A.z * dx) * dx));
@@ -820,7 +854,7 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			if (!FX) {
 				G = gs_exp(power);
 				a0 = B.y * G;
-				live = (pos < lc) & (power <= 0.0f) & (power >= B.w) & (!(a0 < 1.0f / 255.0f));
+				live = (pos < lc) & (power <= 0.0f) & (power >= rc.pcut) & (!(a0 < 1.0f / 255.0f));
 			} else {
 				// gs_exp_hw is valid for every power <= 0, and power < pcut implies opacity * exp(power) < (1/255) exp(-1e-3):
 				// the forward's pcut pre-test is implied by the alpha test

@@ -12,5 +12,8 @@ from .visual_hull import VisualHull, carve, visual_hull_init  # noqa: F401,E402 
 from .voxelize import VoxelGrid, closest_on_mesh, voxel_init, voxel_seeds, voxelize_mesh  # noqa: F401,E402  (mesh -> voxels -> Gaussian seeds)
 # point cloud -> Gaussian seeds; `gaustudio_amd.pcd_init` stays the module (its function of that name is pcd_init.pcd_init)
 from .pcd_init import depth_seeds, mean_dist2, pcd_init_from_ply, point_seeds, sky_seeds  # noqa: F401,E402
+# Scaffold-GS: anchors + MLPs + camera -> Gaussians -> render (the anchor-based family of the reference)
+from .scaffold import (ScaffoldGaussians, ScaffoldModel, decode, decode_torch, render_scaffold,  # noqa: F401,E402
+                       visible_anchors)
 
 __version__ = "0.1.0"

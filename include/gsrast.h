@@ -901,6 +901,36 @@ int gsr_point_seeds(const float* xyz, const float* rgb, const float* dist2, cons
 int gsr_depth_seed_pack(const float* points, const float* image, const float* depth, int num_pixels, float focal, float* xyz,
                         float* rgb, float* scale, void* stream);
 
+/* ---- Scaffold-GS inference in front of the operator (csrc/gsr_scaffold.hip): gaustudio/renderers/scaffold_renderer.py
+ * get_gaussians_properties with its prefilter_voxel, fused into two passes over the anchors.  Additive to ABI 6.  Contract:
+ * INTEGRATION.md s23 (and its definition, tests/scaffold_model.py); design: DESIGN.md s20.  Device memory, f32, contiguous:
+ * anchor [N,3], anchor_feat [N,32], offset [N,k,3], scaling [N,6] and rot [N,4] (both activated), viewmatrix / projmatrix [16]
+ * and campos [3] with the operator's conventions.  weights (HOST array of 16 device pointers): W1, b1, W2, b2 (nn.Linear
+ * layout, W [out,in]) of the opacity MLP (36 -> 32 -> k), the covariance MLP (36 -> 32 -> 7k), the colour MLP (36 -> 32 -> 3k)
+ * and the feature bank (4 -> 32 -> 3; four NULLs = no bank).  1 <= k <= 16, 0 <= N <= 2^24, N k < 2^31 (GSR_ERR_ARG).
+ * Every dot product is bias first, then fma over the ascending input index; bit-identical from run to run. ---- */
+
+/* Pass 1.  visible[a] (u8) = visible_in[a] != 0 when visible_in is given; otherwise radii[a] (i32) = the radius gsr_forward
+ * reports for a Gaussian at anchor[a] with scales scaling[a,0:3] * scale_modifier and rotation rot[a] (0 for a culled one)
+ * and visible[a] = radii[a] > 0 (radii is not written when visible_in is given).  kept[a] (u16): bit j set iff the anchor is
+ * visible and logit j of the opacity MLP is > 0 (a NaN is not).  start[N + 1] (i32): exclusive scan of the bit counts;
+ * *total (HOST) = start[N], read after one wait on `stream`.  Scratch from the allocator callback, once. */
+int gsr_scaffold_count(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* anchor, const float* anchor_feat,
+                       const float* scaling, const float* rot, const float* const weights[16], int num_anchors, int n_offsets,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tanfovx, float tanfovy,
+                       int image_width, int image_height, float scale_modifier, const unsigned char* visible_in,
+                       unsigned char* visible, int* radii, unsigned short* kept, int* start, int* total, void* stream);
+
+/* Pass 2.  For every set bit (a, j) of kept, at row start[a] + (number of set bits of kept[a] below j) -- anchor-major,
+ * offset-minor: xyz [M,3] = anchor + offset[a,j] * scaling[a,0:3]; opacity [M] = tanh(logit); colors [M,3] = sigmoid; scales
+ * [M,3] = scaling[a,3:6] * sigmoid(o[0:3]); rotations [M,4] = o[3:7] / max(|o[3:7]|, 1e-12); anchor_index / offset_index [M]
+ * i32.  tanh and sigmoid from the library's polynomial exp.  num_gaussians = *total of pass 1; an
+ * anchor whose rows would not fit [0, num_gaussians) writes nothing.  No wait. */
+int gsr_scaffold_emit(const float* anchor, const float* anchor_feat, const float* offset, const float* scaling,
+                      const float* const weights[16], int num_anchors, int n_offsets, const float* campos, const unsigned short* kept,
+                      const int* start, int num_gaussians, float* xyz, float* colors, float* opacity, float* scales, float* rotations,
+                      int* anchor_index, int* offset_index, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

@@ -8,10 +8,13 @@ get_gaussians_properties and prefilter_voxel).
     g = decode(model, view)                                        # ScaffoldGaussians: two HIP passes over the anchors
     g = decode_torch(model, view, mask)                            # the same in plain torch ops: any device, differentiable
     out = render_scaffold(model, camera_settings)                  # decode + GaussianRasterizer(colors_precomp)
+    g = decode(model, view, backward="hip")                        # training: the same forward, gradients by the HIP backward
+    out = render_scaffold(model, camera_settings, backward="hip")
 
 `view` / `camera_settings` is the operator's GaussianRasterizationSettings.  Contract, quirks and what is unsupported:
-INTEGRATION.md s23; the definition of every bit `decode` returns is tests/scaffold_model.py.  `decode` takes ROCm tensors only
-and has no CPU fallback; every call runs on the current stream of the tensors' device.
+INTEGRATION.md s23 (the gradient: s23a); the definition of every bit `decode` returns is tests/scaffold_model.py, of every bit
+of its HIP gradient tests/scaffold_grad_model.py.  `decode` takes ROCm tensors only and has no CPU fallback; every call runs
+on the current stream of the tensors' device.
 """
 import ctypes
 from typing import NamedTuple, Optional, Tuple
@@ -265,7 +268,7 @@ def visible_anchors(model, view):
     return visible, radii
 
 
-def decode(model, view, visible_mask=None):
+def decode(model, view, visible_mask=None, backward="torch"):
     """The Gaussians of one view (ScaffoldGaussians), by two HIP passes over the anchors (csrc/gsr_scaffold.hip): count (filter,
     view direction, feature bank, opacity MLP, scan) and emit (covariance and colour MLPs, activations, compaction), with one
     4-byte read-back in between.  visible_mask (bool [N]) replaces the camera test.  ROCm tensors only.
@@ -276,11 +279,19 @@ def decode(model, view, visible_mask=None):
     order; tanh, sigmoid and the bank's softmax come from the library's polynomial exp.  Two calls return the same bits, and
     tests/scaffold_model.py reproduces them on a CPU.
 
-    TRAINING: when grad mode is on and any tensor of the model requires grad, decode dispatches to decode_torch -- the
-    differentiable restatement in torch ops -- with the mask of visible_anchors (or the caller's).  Its logits differ from the
-    HIP path's in the last bits (torch's GEMM sums in another order), so an offset whose logit is within rounding of 0 can be
-    kept by one path and dropped by the other."""
+    TRAINING: when grad mode is on and any tensor of the model requires grad, `backward` chooses the differentiable path.
+    "torch" (the default): decode dispatches to decode_torch -- the differentiable restatement in torch ops -- with the mask of
+    visible_anchors (or the caller's).  Its logits differ from the HIP path's in the last bits (torch's GEMM sums in another
+    order), so an offset whose logit is within rounding of 0 can be kept by one path and dropped by the other.
+    "hip": the two HIP passes above stay the forward (the same bits as under no_grad) and the gradient is the HIP backward
+    gsr_scaffold_backward (tests/scaffold_grad_model.py defines its bits): d anchor, anchor_feat, offset,
+    scaling and the weights of every MLP; the visible mask, the kept mask, rot and the camera are constants.  Under no_grad, or
+    with nothing requiring grad, `backward` changes nothing."""
+    if backward not in ("torch", "hip"):
+        raise ValueError(f"backward must be 'torch' or 'hip', got {backward!r}")
     if torch.is_grad_enabled() and model.check().requires_grad():
+        if backward == "hip":
+            return _decode_hip_grad(model, view, visible_mask)
         if visible_mask is None:
             with torch.no_grad():
                 visible_mask, radii = visible_anchors(model, view)
@@ -304,21 +315,107 @@ def _emit(model, counted):
     return ScaffoldGaussians(xyz, colors, opacity, scales, rotations, aidx, oidx, visible, radii)
 
 
+_GRAD_ATTRS = ("anchor", "anchor_feat", "offset", "scaling")
+
+
+def _pointer_table(tensors):
+    arr = (ctypes.c_void_p * 16)()
+    for i, t in enumerate(tensors):
+        arr[i] = None if t is None else t.data_ptr()
+    return arr
+
+
+class _DecodeHip(torch.autograd.Function):
+    """decode with the HIP backward.  Inputs: the model and the view (plain objects), then the differentiable tensors: anchor,
+    anchor_feat, offset, scaling and the 12 or 16 MLP tensors.  Saved: those, campos, kept, start; M."""
+
+    @staticmethod
+    def forward(ctx, model, view, visible_mask, *tensors):
+        counted = _count(model, view, visible_mask, "decode")
+        g = _emit(model, counted)
+        visible, radii, kept, start, m, a, (warr, wkeep), cam = counted
+        ctx.save_for_backward(*(a[name] for name in _GRAD_ATTRS), *wkeep, cam["campos"], kept, start)
+        ctx.num_gaussians, ctx.n_offsets, ctx.bank = m, model.n_offsets, model.use_feat_bank
+        nondiff = (g.anchor_index, g.offset_index, g.visible) + (() if radii is None else (radii,))
+        ctx.mark_non_differentiable(*nondiff)
+        return (g.xyz, g.colors, g.opacity, g.scales, g.rotations) + nondiff
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xyz, g_col, g_op, g_sc, g_rot, *_):
+        saved = ctx.saved_tensors
+        anchor, feat, offset, scaling = saved[:4]
+        nw = 16 if ctx.bank else 12
+        weights, (campos, kept, start) = saved[4:4 + nw], saved[4 + nw:]
+        dev, m, k, n = anchor.device, ctx.num_gaussians, ctx.n_offsets, anchor.shape[0]
+        cots = {}
+        for name, t, cols in (("xyz", g_xyz, 3), ("colors", g_col, 3), ("opacity", g_op, 1), ("scales", g_sc, 3), ("rotations", g_rot, 4)):
+            if t is not None:
+                if t.dtype != torch.float32 or tuple(t.shape) != (m, cols):
+                    raise ValueError(f"decode backward: the cotangent of {name} must be float32 [{m}, {cols}], got {t.dtype} "
+                                     f"{list(t.shape)}")
+                t = t.contiguous()
+            cots[name] = t
+        on_rocm(**{"grad_" + name: t for name, t in cots.items()})
+        same_device(dev, ref="anchor", **{"grad_" + name: t for name, t in cots.items()})
+        d_attr = [torch.empty_like(t) for t in (anchor, feat, offset, scaling)]
+        d_w = [torch.empty_like(t) for t in weights]
+        if n > 0:
+            call("gsr_scaffold_backward", dev, anchor, feat, offset, scaling, _pointer_table(list(weights) + [None] * (16 - nw)), n, k,
+                 campos, kept, start, m, cots["xyz"], cots["colors"], cots["opacity"], cots["scales"], cots["rotations"], *d_attr,
+                 _pointer_table(d_w + [None] * (16 - nw)), workspace=True, what="decode backward", errors=_ERRORS)
+        else:
+            for t in d_w:
+                t.zero_()
+        grads = d_attr + d_w
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
+def _decode_hip_grad(model, view, visible_mask):
+    ts = [getattr(model, name) for name in _GRAD_ATTRS]
+    for m in ScaffoldModel._MLPS:
+        if getattr(model, m) is not None:
+            ts.extend(getattr(model, m))
+    out = _DecodeHip.apply(model, view, visible_mask, *ts)
+    return ScaffoldGaussians(*out[:8], out[8] if len(out) > 8 else None)
+
+
+def _kept_bool(model, kept):
+    """decode_torch's kept argument as bool [N, k]: a bool [N, k] tensor, or the bit mask [N] (uint16 / int16, bit j = offset j)
+    that the HIP passes use."""
+    n, k = model.num_anchors, model.n_offsets
+    if not torch.is_tensor(kept):
+        raise TypeError("kept must be a torch tensor or None")
+    if kept.dtype == torch.bool:
+        if tuple(kept.shape) != (n, k):
+            raise ValueError(f"a bool kept must have shape [{n}, {k}], got {list(kept.shape)}")
+        return kept
+    if kept.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        raise TypeError(f"kept must be bool [N, k] or a 16-bit mask [N] (uint16 / int16), got {kept.dtype}")
+    if tuple(kept.shape) != (n,):
+        raise ValueError(f"a bit-mask kept must have shape [{n}], got {list(kept.shape)}")
+    bits = kept.view(torch.int16).to(torch.int32) & 0xFFFF
+    return ((bits[:, None] >> torch.arange(k, device=kept.device, dtype=torch.int32)[None, :]) & 1).bool()
+
+
 def _mlp(w, x):
     return F.linear(torch.relu(F.linear(x, w[0], w[1])), w[2], w[3])
 
 
-def decode_torch(model, view, visible_mask=None):
-    """get_gaussians_properties restated in plain torch ops: runs on any device, is differentiable, and is the training path
-    (decode dispatches here under grad).  visible_mask bool [N]; None = every anchor.  Returns ScaffoldGaussians with radii =
-    None.  The logits differ from decode's in the last bits, because torch's GEMM sums in a different order: compare the two
-    within a bound, never for equality."""
+def decode_torch(model, view, visible_mask=None, kept=None):
+    """get_gaussians_properties restated in plain torch ops: runs on any device, is differentiable, and is the default training
+    path (decode dispatches here under grad).  visible_mask bool [N]; None = every anchor.  Returns ScaffoldGaussians with
+    radii = None.  The logits differ from decode's in the last bits, because torch's GEMM sums in a different order: compare
+    the two within a bound, never for equality.  kept (bool [N, k], or the bit mask [N] of the HIP passes) replaces the
+    `logit > 0` rule for the visible anchors, so that both paths can work on the same set of Gaussians."""
     model.check()
+    kept = None if kept is None else _kept_bool(model, kept)
     _check_view(view, need_camera=False)
     mask = _check_mask(model, visible_mask)
     n, k = model.num_anchors, model.n_offsets
     dev = model.anchor.device
-    same_device(dev, ref="anchor", **{name: t for name, t in model.tensors().items() if name != "anchor"}, visible_mask=mask)
+    same_device(dev, ref="anchor", **{name: t for name, t in model.tensors().items() if name != "anchor"}, visible_mask=mask,
+                kept=kept)
     if mask is None:
         mask = torch.ones(n, dtype=torch.bool, device=dev)
     feat, anchor = model.anchor_feat[mask], model.anchor[mask]
@@ -331,7 +428,7 @@ def decode_torch(model, view, visible_mask=None):
         feat = feat[:, ::4].repeat(1, 4) * w[:, 0:1] + feat[:, ::2].repeat(1, 2) * w[:, 1:2] + feat * w[:, 2:3]
     x = torch.cat([feat, ob_view, ob_dist], dim=1)
     logit = _mlp(model.mlp_opacity, x).reshape(-1)
-    keep = logit > 0.0
+    keep = logit > 0.0 if kept is None else kept[mask].reshape(-1)
     color = torch.sigmoid(_mlp(model.mlp_color, x)).reshape(-1, 3)[keep]
     cov = _mlp(model.mlp_cov, x).reshape(-1, 7)[keep]
     rep = lambda t: t.repeat_interleave(k, dim=0)[keep]
@@ -345,17 +442,18 @@ def decode_torch(model, view, visible_mask=None):
         offset_index=(flat % k).to(torch.int32), visible=mask, radii=None)
 
 
-def render_scaffold(model, camera_settings, bg=None, visible_mask=None, kernel_size=0.0, subpixel_offset=None):
+def render_scaffold(model, camera_settings, bg=None, visible_mask=None, kernel_size=0.0, subpixel_offset=None, backward="torch"):
     """ScaffoldRenderer.render: decode, then the operator with colors_precomp.  Returns the reference's dict -- `render`,
     `viewspace_points`, `visibility_filter`, `radii` -- plus `depth`, `median_depth`, `opacity` (this operator's other outputs)
     and `gaussians` (the ScaffoldGaussians).  bg replaces camera_settings.bg.  kernel_size and subpixel_offset are the
-    arguments of a rasterizer fork the vendored operator is not: anything but 0 / None raises."""
+    arguments of a rasterizer fork the vendored operator is not: anything but 0 / None raises.  backward: decode's ("torch" or
+    "hip": which decoder gradient trains the model)."""
     if kernel_size not in (0, 0.0) or isinstance(kernel_size, bool):
         raise NotImplementedError("render_scaffold: kernel_size is not supported (the operator has no 3D filter); pass 0")
     if subpixel_offset is not None:
         raise NotImplementedError("render_scaffold: subpixel_offset is not supported")
     from .rasterizer import GaussianRasterizer
-    g = decode(model, camera_settings, visible_mask)
+    g = decode(model, camera_settings, visible_mask, backward=backward)
     rs = camera_settings if bg is None else camera_settings._replace(bg=bg)
     screenspace = torch.zeros_like(g.xyz, requires_grad=True) + 0
     try:

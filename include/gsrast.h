@@ -931,6 +931,24 @@ int gsr_scaffold_emit(const float* anchor, const float* anchor_feat, const float
                       const int* start, int num_gaussians, float* xyz, float* colors, float* opacity, float* scales, float* rotations,
                       int* anchor_index, int* offset_index, void* stream);
 
+/* The gradient of the two passes above (its definition: tests/scaffold_grad_model.py; design: DESIGN.md
+ * s20a).  kept / start / num_gaussians: what pass 1 returned for the same inputs; the forward values are recomputed from them
+ * by the forward's own code.  g_xyz [M,3], g_colors [M,3], g_opacity [M], g_scales [M,3], g_rotations [M,4]: the cotangents of
+ * pass 2's outputs in its row order, contiguous; NULL = zeros.  Outputs, all written (zero rows for invisible anchors, for
+ * anchors without a kept offset and for dropped offsets): d_anchor [N,3], d_anchor_feat [N,32], d_offset [N,k,3], d_scaling
+ * [N,6]; d_weights (HOST array of 16 device pointers, laid out as `weights`, the bank's four NULL iff the bank's are): the
+ * gradients of W1, b1, W2, b2 of each MLP.  The visible mask, the kept mask, rot, campos and the camera are constants.  The
+ * sums over anchors follow a fixed tree (256-anchor blocks dealt to 256 chains, block b to chain b mod 256; ascending within
+ * a chain; the chains added in ascending order in f64): no atomics, bit-identical from run to run and on any stream.  With
+ * num_gaussians == 0 no kernel is launched and every output is zero.  Scratch from the allocator callback, once: at most
+ * 65536 anchors are staged at a time.  No wait. */
+int gsr_scaffold_backward(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* anchor, const float* anchor_feat,
+                          const float* offset, const float* scaling, const float* const weights[16], int num_anchors, int n_offsets,
+                          const float* campos, const unsigned short* kept, const int* start, int num_gaussians, const float* g_xyz,
+                          const float* g_colors, const float* g_opacity, const float* g_scales, const float* g_rotations,
+                          float* d_anchor, float* d_anchor_feat, float* d_offset, float* d_scaling, float* const d_weights[16],
+                          void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

@@ -4,7 +4,9 @@
   * decode's two passes (count: filter-by-mask, view direction, bank, opacity MLP, scan, the 4-byte read-back; emit: covariance
     and colour MLPs, activations, compaction) and the whole call;
   * decode_torch (get_gaussians_properties in plain torch ops, under no_grad) for the SAME visible mask on the same GPU;
-  * N = 1e5 and 1e6 anchors, k = 10, with and without the feature bank, about 30 % and 100 % of the anchors visible.
+  * N = 1e5 and 1e6 anchors, k = 10, with and without the feature bank, about 30 % and 100 % of the anchors visible;
+  * per case a `training` block: forward + backward of decode(backward="hip") against decode(backward="torch") with the same
+    mask and cotangents, and the peak memory of each (see training()).
 
     python tools/scaffold_timing.py [--repeat 7] [--sizes 100000 1000000] [--out profiles/scaffold_timing.json]
 Every figure is the median of --repeat calls after one warm-up call per variant, with the min-max spread beside it; the variants
@@ -57,6 +59,58 @@ def summary(xs):
     return dict(median_ms=round(statistics.median(xs), 4), min_ms=round(min(xs), 4), max_ms=round(max(xs), 4))
 
 
+OUTS = ("xyz", "colors", "opacity", "scales", "rotations")
+
+
+def training(model, view, mask, repeat):
+    """Forward + backward of decode(backward="hip") against decode(backward="torch") (decode_torch under autograd: what trains a
+    model without the HIP backward): every tensor of the model but rot requires grad, the same visible mask, the same seeded
+    cotangents of the five outputs when both paths keep the same number of Gaussians (otherwise each path gets its own, and
+    `same_cotangents` says so).  Per path: median (min, max) of `repeat` calls after one warm-up, alternated, host clocks around
+    a call that ends in a device synchronise; peak_mib = torch.cuda.max_memory_allocated over one call minus what was
+    allocated before it."""
+    leaves = [t for name, t in model.tensors().items() if name != "rot"]
+    for t in leaves:
+        t.requires_grad_(True)
+    dev = model.anchor.device
+    cots = {}
+
+    def cot(m):
+        if m not in cots:
+            g = torch.Generator(device="cpu").manual_seed(11)
+            cots[m] = [torch.randn(m, c, generator=g).to(dev) for c in (3, 3, 1, 3, 4)]
+        return cots[m]
+
+    def step(path):
+        for t in leaves:
+            t.grad = None
+        g = sc.decode(model, view, mask, backward=path)
+        torch.autograd.backward([getattr(g, n) for n in OUTS], cot(g.xyz.shape[0]))
+        return int(g.xyz.shape[0])
+
+    ts, peak, rows = dict(hip=[], torch=[]), {}, {}
+    for path in ts:
+        rows[path] = step(path)                                   # warm-up (and the cotangents)
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        step(path)
+        torch.cuda.synchronize()
+        peak[path] = round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+    for _ in range(repeat):
+        for path in ts:
+            ts[path].append(wall(lambda: step(path))[0])
+    for t in leaves:
+        t.grad = None
+        t.requires_grad_(False)
+    out = dict(gaussians=rows, same_cotangents=rows["hip"] == rows["torch"],
+               hip=dict(summary(ts["hip"]), peak_mib=peak["hip"]), torch=dict(summary(ts["torch"]), peak_mib=peak["torch"]))
+    out["torch_over_hip"] = round(out["torch"]["median_ms"] / out["hip"]["median_ms"], 3)
+    spreads = (out["hip"]["max_ms"] - out["hip"]["min_ms"]) + (out["torch"]["max_ms"] - out["torch"]["min_ms"])
+    out["hip_below_torch_by_more_than_both_spreads"] = bool(out["torch"]["median_ms"] - out["hip"]["median_ms"] > spreads)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=7)
@@ -96,6 +150,7 @@ def main():
                                                             if g.xyz.shape[0] == t.xyz.shape[0] and g.xyz.shape[0] else None),
                              **{name: summary(v) for name, v in ts.items()})
                 entry["decode_torch_over_decode"] = round(entry["decode_torch"]["median_ms"] / entry["decode"]["median_ms"], 3)
+                entry["training"] = training(model, view, mask, args.repeat)
                 res["cases"].append(entry)
                 print(json.dumps(entry), flush=True)
                 del g, t, mask

@@ -1,5 +1,8 @@
 #!/usr/bin/env python
-"""Generates gsr_mc_tables.h: the 256-case marching-cubes triangle table used by csrc/gsr_tsdf.hip.
+"""Generates gsr_mc_tables.h: the 256-case marching-cubes triangle table and the cube geometry (corner offsets, the owner and
+the axis of every edge) that every marching-cubes extractor of the library reads: the block kernels of the two sparse
+volumes (csrc/gsr_block_volume.h, csrc/gsr_tsdf.hip) and the dense-grid kernels of csrc/gsr_psr.hip.  Under hipcc the tables
+are statically initialised __constant__ arrays: compile-time data of the code object, nothing to upload at run time.
 
 The tables are DERIVED here, not transcribed: for every sign configuration of the eight cube corners the
 isosurface inside the cube is assembled from oriented segments on the six faces and the resulting closed loops are
@@ -103,19 +106,45 @@ def build():
     return table, edge_mask
 
 
+def edge_geometry():
+    """Per cube edge the corner that owns it and its axis.  A vertex on an edge is stored once, with the voxel (or grid node) at
+    the edge's end with the smaller coordinates: the owner; the axis is the coordinate in which the two ends differ."""
+    owner, axis = [], []
+    for a, b in EDGES:
+        diff = [d for d in range(3) if CORNERS[a][d] != CORNERS[b][d]]
+        assert len(diff) == 1, (a, b)
+        owner.append(min(a, b, key=lambda c: CORNERS[c]))
+        axis.append(diff[0])
+    # the values the kernels were written against
+    assert owner == [0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3], owner
+    assert axis == [0, 1, 0, 1, 0, 1, 0, 1, 2, 2, 2, 2], axis
+    return owner, axis
+
+
 def header_text():
     table, edge_mask = build()
+    owner, axis = edge_geometry()
     maxt = max(len(t) for t in table)
     out = ["// gsr_mc_tables.h -- GENERATED by gen_mc_tables.py (derived marching-cubes tables; do not edit).",
            "#pragma once",
            "#include <stdint.h>",
            f"#define GSR_MC_MAX_TRIS {maxt}",
+           "// device code reads the tables from constant memory of its own code object; they are never written",
+           "#ifdef __HIPCC__",
+           "#define GSR_MC_TABLE static __device__ __constant__ const",
+           "#else",
+           "#define GSR_MC_TABLE static const",
+           "#endif",
+           "// cube corner offsets and, per cube edge, the corner that owns it (the end with the smaller coordinates) and its axis",
+           "GSR_MC_TABLE int gsr_mc_corner[8][3] = {" + ", ".join("{%d, %d, %d}" % c for c in CORNERS) + "};",
+           "GSR_MC_TABLE uint8_t gsr_mc_edge_owner[12] = {" + ", ".join(str(v) for v in owner) + "};",
+           "GSR_MC_TABLE uint8_t gsr_mc_edge_axis[12] = {" + ", ".join(str(v) for v in axis) + "};",
            "// number of triangles per case",
-           "static const uint8_t gsr_mc_ntris[256] = {" + ", ".join(str(len(t)) for t in table) + "};",
+           "GSR_MC_TABLE uint8_t gsr_mc_ntris[256] = {" + ", ".join(str(len(t)) for t in table) + "};",
            "// bit e set: edge e carries a vertex in this case",
-           "static const uint16_t gsr_mc_edge_mask[256] = {" + ", ".join(str(m) for m in edge_mask) + "};",
-           f"// triangles as edge triples, padded with 255",
-           f"static const uint8_t gsr_mc_tris[256][{3 * maxt}] = {{"]
+           "GSR_MC_TABLE uint16_t gsr_mc_edge_mask[256] = {" + ", ".join(str(m) for m in edge_mask) + "};",
+           "// triangles as edge triples, padded with 255",
+           f"GSR_MC_TABLE uint8_t gsr_mc_tris[256][{3 * maxt}] = {{"]
     for t in table:
         flat = [e for tri in t for e in tri]
         flat += [255] * (3 * maxt - len(flat))

@@ -296,64 +296,4 @@ void launch_surfel_preprocess_bwd(int P, int W, int H, const float* means3D, con
                                   const uint32_t* goff, const float* rows, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor,
                                   float* dL_dmean3D, float* dL_dscale, float* dL_drot, hipStream_t s);
 
-// --- block hash of the sparse volumes (gsr_tsdf.hip, gsr_tsdf_rgbd.hip): 8^3-voxel blocks, 64-bit keys of three 21-bit
-// biased block coordinates, open addressing with linear probing; a block's voxels live at its hash slot ---
-constexpr uint64_t TSDF_EMPTY = ~0ull;
-constexpr int TSDF_BLOCK_VOX = 512;
-constexpr int TSDF_BLOCK_BIAS = 1 << 20;   // block coordinates in (-2^20, 2^20)
-
-__host__ __device__ __forceinline__ uint64_t tsdf_block_key(int bx, int by, int bz)
-{
-	const uint64_t B = 1u << 20;
-	return ((uint64_t)(bx + (int)B) << 42) | ((uint64_t)(by + (int)B) << 21) | (uint64_t)(bz + (int)B);
-}
-__host__ __device__ __forceinline__ void tsdf_decode_key(uint64_t key, int& bx, int& by, int& bz)
-{
-	const int B = 1 << 20;
-	bx = (int)((key >> 42) & 0x1fffff) - B;
-	by = (int)((key >> 21) & 0x1fffff) - B;
-	bz = (int)(key & 0x1fffff) - B;
-}
-#ifdef __HIPCC__
-__device__ __forceinline__ uint64_t tsdf_mix64(uint64_t x)
-{
-	x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-	x ^= x >> 27; x *= 0x94d049bb133111ebull;
-	x ^= x >> 31;
-	return x;
-}
-// returns the slot of `key`, inserting it if absent; -1 when the table is full (probe limit)
-__device__ inline int64_t tsdf_find_or_insert(unsigned long long* keys, uint64_t mask, uint64_t key)
-{
-	uint64_t slot = tsdf_mix64(key) & mask;
-	for (uint64_t probe = 0; probe <= mask; probe++) {
-		unsigned long long k = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
-		if (k == key) return (int64_t)slot;
-		if (k == TSDF_EMPTY) {
-			const unsigned long long old = atomicCAS(&keys[slot], (unsigned long long)TSDF_EMPTY, (unsigned long long)key);
-			if (old == TSDF_EMPTY || old == key) return (int64_t)slot;
-		}
-		slot = (slot + 1) & mask;
-	}
-	return -1;
-}
-__device__ inline int64_t tsdf_find_slot(const unsigned long long* keys, uint64_t mask, uint64_t key)
-{
-	uint64_t slot = tsdf_mix64(key) & mask;
-	for (uint64_t probe = 0; probe <= mask; probe++) {
-		const unsigned long long k = keys[slot];
-		if (k == key) return (int64_t)slot;
-		if (k == TSDF_EMPTY) return -1;
-		slot = (slot + 1) & mask;
-	}
-	return -1;
-}
-#endif
-// The two voxel-format-independent passes of the block marching cubes (gsr_tsdf.hip): per-block vertex / triangle totals from
-// cases[] and edge_flags[], and the triangles through the edge owners' vertex_base[].  Return GSR_OK or GSR_ERR_HIP.
-int launch_tsdf_mc_count(int num_blocks, const uint8_t* cases, const uint32_t* flags, uint32_t* block_nv, uint32_t* block_nt, hipStream_t s);
-int launch_tsdf_mc_triangles(const uint64_t* keys, uint64_t capacity, const uint32_t* blocks, int num_blocks, const uint32_t* cidx,
-                             const uint8_t* cases, const uint32_t* flags, const uint32_t* vbase, const uint32_t* block_toff,
-                             int* triangles, hipStream_t s);
-
 }  // namespace gsr

@@ -10,7 +10,8 @@
 //   * spectral solve: the reference's fp32 chain per element, the Gaussian filter evaluated in fp64 and cast;
 //   * grid_interp: the 8 corner terms lat * w (fp32) added in fp64 in the reference's corner order, rounded once; the mean of
 //     the samples is a fixed-order fp64 reduction;
-//   * marching cubes: inside iff value < level, tables of gsr_mc_tables.h, one vertex per crossing edge owned by the edge's
+//   * marching cubes: inside iff value < level, tables and cube geometry of gsr_mc_tables.h (constants of the code object, the
+//     ones the block volumes read), one vertex per crossing edge owned by the edge's
 //     lower node, vertices ordered by (owner node linear index, axis), triangles by (cube linear index, table order).
 //
 // MI355X design:
@@ -276,25 +277,8 @@ __global__ void __launch_bounds__(256) psr_normalize(const float* in, float* out
 }
 
 // ------------------------------------------------------------------------------------------------------ marching cubes
-__device__ __constant__ uint8_t p_ntris[256];
-__device__ __constant__ uint8_t p_tris[256][3 * GSR_MC_MAX_TRIS];
-// cube corner offsets along (axis 0, axis 1, axis 2) and, per cube edge, the corner that owns it (its lower end) and its axis
-__device__ __constant__ int p_corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
-__device__ __constant__ uint8_t p_edge_owner[12] = {0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3};
-__device__ __constant__ uint8_t p_edge_axis[12] = {0, 1, 0, 1, 0, 1, 0, 1, 2, 2, 2, 2};
-
-bool g_psr_tables_loaded[16] = {};
-int load_tables()
-{
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return GSR_ERR_HIP;
-	if (g_psr_tables_loaded[dev]) return GSR_OK;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(p_ntris), gsr_mc_ntris, sizeof(gsr_mc_ntris)) != hipSuccess) return GSR_ERR_HIP;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(p_tris), gsr_mc_tris, sizeof(gsr_mc_tris)) != hipSuccess) return GSR_ERR_HIP;
-	g_psr_tables_loaded[dev] = true;
-	return GSR_OK;
-}
-
+// tables and cube geometry (corner offsets along axis 0, 1, 2; per cube edge the corner that owns it -- its lower end -- and its
+// axis): gsr_mc_tables.h, the ones the block volumes use.  The kernels are this file's own: one lane per node of a dense grid.
 // per node: info = cube case (cube with this node as its lower corner; 0 on the upper faces of the grid) | edge flags << 8
 // (bit a: the edge from this node along axis a crosses the level), and the two counts the scans run over
 __global__ void __launch_bounds__(256) psr_mc_classify(const float* __restrict__ g, int r0, int r1, int r2, float level,
@@ -313,11 +297,11 @@ __global__ void __launch_bounds__(256) psr_mc_classify(const float* __restrict__
 	uint32_t cs = 0;
 	if (has[0] && has[1] && has[2]) {
 		for (int c = 0; c < 8; c++)
-			if (g[lin + p_corner[c][0] * st[0] + p_corner[c][1] * st[1] + p_corner[c][2] * st[2]] < level) cs |= 1u << c;
+			if (g[lin + gsr_mc_corner[c][0] * st[0] + gsr_mc_corner[c][1] * st[1] + gsr_mc_corner[c][2] * st[2]] < level) cs |= 1u << c;
 	}
 	info[lin] = cs | (fl << 8);
 	nvc[lin] = __popc(fl);
-	ntc[lin] = p_ntris[cs];
+	ntc[lin] = gsr_mc_ntris[cs];
 }
 
 __global__ void __launch_bounds__(256) psr_mc_vertices(const float* __restrict__ g, int r0, int r1, int r2, float level,
@@ -351,15 +335,15 @@ __global__ void __launch_bounds__(256) psr_mc_triangles(int r0, int r1, int r2, 
 	const long long lin = (long long)blockIdx.x * 256 + threadIdx.x;
 	if (lin >= nn) return;
 	const uint32_t cs = info[lin] & 255u;
-	const int nt = p_ntris[cs];
+	const int nt = gsr_mc_ntris[cs];
 	if (!nt) return;
 	const long long st[3] = {(long long)r1 * r2, r2, 1};
 	size_t t = (size_t)toff[lin];
 	for (int q = 0; q < nt; q++, t++) {
 		for (int c = 0; c < 3; c++) {
-			const int e = p_tris[cs][3 * q + c];
-			const int o = p_edge_owner[e], ax = p_edge_axis[e];
-			const long long ol = lin + p_corner[o][0] * st[0] + p_corner[o][1] * st[1] + p_corner[o][2] * st[2];
+			const int e = gsr_mc_tris[cs][3 * q + c];
+			const int o = gsr_mc_edge_owner[e], ax = gsr_mc_edge_axis[e];
+			const long long ol = lin + gsr_mc_corner[o][0] * st[0] + gsr_mc_corner[o][1] * st[1] + gsr_mc_corner[o][2] * st[2];
 			const uint32_t fl = info[ol] >> 8;
 			faces[3 * t + c] = voff[ol] + __popc(fl & ((1u << ax) - 1u));
 		}
@@ -672,15 +656,13 @@ int gsr_psr_mc_classify(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const
 {
 	if (!grid || !good_res(r0, r1, r2) || !node_info || !vertex_offset || !triangle_offset || !num_vertices || !num_triangles)
 		return GSR_ERR_ARG;
-	int rc = load_tables();
-	if (rc) return rc;
 	hipStream_t s = (hipStream_t)stream;
 	const long long nn = (long long)r0 * r1 * r2;
 	int *nvc, *ntc, *part;
 	auto carve = [&](Arena& ws) { nvc = ws.take<int>(nn); ntc = ws.take<int>(nn); part = ws.take<int>(scan_part_len(nn)); };
 	if (!ws_carve(workspace_alloc, workspace_ctx, carve)) return GSR_ERR_ALLOC;
 	hipLaunchKernelGGL(psr_mc_classify, dim3(blocks(nn)), dim3(256), 0, s, grid, r0, r1, r2, level, node_info, nvc, ntc);
-	rc = exclusive_scan(nvc, (int)nn, vertex_offset, part, s);
+	int rc = exclusive_scan(nvc, (int)nn, vertex_offset, part, s);
 	if (rc) return rc;
 	rc = exclusive_scan(ntc, (int)nn, triangle_offset, part, s);
 	if (rc) return rc;
@@ -694,8 +676,6 @@ int gsr_psr_mc_emit(const float* grid, int r0, int r1, int r2, float level, cons
                     const int* triangle_offset, float* vertices, int* faces, void* stream)
 {
 	if (!grid || !good_res(r0, r1, r2) || !node_info || !vertex_offset || !triangle_offset) return GSR_ERR_ARG;
-	const int rc = load_tables();
-	if (rc) return rc;
 	hipStream_t s = (hipStream_t)stream;
 	const long long nn = (long long)r0 * r1 * r2;
 	if (vertices) hipLaunchKernelGGL(psr_mc_vertices, dim3(blocks(nn)), dim3(256), 0, s, grid, r0, r1, r2, level, node_info, vertex_offset, vertices);

@@ -17,34 +17,24 @@
 //     one integer atomicAdd per update, order-independent => bit-deterministic fusion (a float running average is
 //     order dependent); mean tsdf = sum_q / count * sdf_trunc / 2^15.  Field widths: 24-bit count and 40-bit
 //     signed sum hold 2^24 - 1 observations of a voxel at full magnitude (|tsdf| = sdf_trunc) -- the limit of the format;
-//   * extraction: marching cubes with tables derived in gen_mc_tables.py, shared vertices (each voxel owns the
-//     three edges leaving its minimum corner), count -> scan -> emit, no atomics in the emit passes.
+//   * extraction: the block marching cubes of gsr_block_volume.h (classify -> count -> scan -> vertices -> triangles, shared
+//     vertices, tables derived in gen_mc_tables.py).  This file gives it the packed voxels as a format (PackedVoxels) and holds
+//     the two passes that read no voxels, count and triangles, for every format.
 // All state is caller-owned device memory (torch tensors in gaustudio_amd/tsdf.py); the entry points are stateless.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gsrast.h"
-#include "gsr_internal.h"
-#include "gsr_mc_tables.h"
+#include "gsr_block_volume.h"
 
 namespace {
 
 constexpr int BLOCK_VOX = gsr::TSDF_BLOCK_VOX;
 constexpr float QSCALE = 32768.0f;   // 2^15: 2^24 observations x 2^15 fit the 40-bit signed sum field
 
-__device__ __constant__ uint8_t d_ntris[256];
-__device__ __constant__ uint16_t d_edge_mask[256];
-__device__ __constant__ uint8_t d_tris[256][3 * GSR_MC_MAX_TRIS];
-// cube corner offsets and, per cube edge, the corner that owns it (the edge's minimum corner) and its axis
-__device__ __constant__ int d_corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
-__device__ __constant__ uint8_t d_edge_owner[12] = {0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3};
-__device__ __constant__ uint8_t d_edge_axis[12] = {0, 1, 0, 1, 0, 1, 0, 1, 2, 2, 2, 2};
-
-// block keys and the hash probes: gsr_internal.h (shared with gsr_tsdf_rgbd.hip)
+using gsr::pow2;
 using gsr::tsdf_block_key;
-using gsr::tsdf_decode_key;
 using gsr::tsdf_find_or_insert;
-using gsr::tsdf_find_slot;
 
 // OpenVDB math::MinIndex: index of the smallest component with its tie-breaking table
 __device__ __forceinline__ int min_index(float a, float b, float c)
@@ -244,76 +234,32 @@ __global__ __launch_bounds__(512) void tsdf_export_kernel(const unsigned long lo
 	sums[dst] = (long long)vox[src] >> 24;
 }
 
-// ---- marching cubes over the occupied blocks (blocks[] = hash slots in a caller-chosen, deterministic order) ----
-// s_nb[8]: hash slots of the 2x2x2 blocks starting at the workgroup's block (-1 = absent), index dz*4+dy*2+dx
-// value of the voxel at local coordinates (lx,ly,lz) in [0,8] of the 2x2x2 block neighbourhood; false = block absent
-__device__ __forceinline__ bool fetch(const unsigned long long* __restrict__ vox, const int64_t* nb, int lx, int ly, int lz,
-                                      float sdf_trunc, float& f, uint32_t& c)
-{
-	const int64_t s = nb[((lz >> 3) << 2) | ((ly >> 3) << 1) | (lx >> 3)];
-	if (s < 0) { f = sdf_trunc; c = 0; return false; }
-	unpack(vox[(size_t)s * BLOCK_VOX + (((lz & 7) << 6) | ((ly & 7) << 3) | (lx & 7))], sdf_trunc, f, c);
-	return true;
-}
-
-// case index of the cube whose minimum corner is this voxel; 0 when the cube is not extractable
-__device__ __forceinline__ int cube_case(const unsigned long long* __restrict__ vox, const int64_t* nb, int lx, int ly, int lz,
-                                         float sdf_trunc, uint32_t min_count, int fill_holes, float* fout)
-{
-	int idx = 0;
-#pragma unroll
-	for (int i = 0; i < 8; i++) {
-		float f;
+// ---- marching cubes over the occupied blocks: the scheme of gsr_block_volume.h ----
+// the packed voxels as its voxel format.  Weights are integer counts: weight < min_weight  <=>  count < min_count = ceil(min_weight)
+struct PackedVoxels {
+	static constexpr int SLOT_ELEMS = BLOCK_VOX;
+	static constexpr bool COLORS = false;
+	const unsigned long long* vox;
+	float voxel, sdf_trunc;
+	uint32_t min_count;
+	int fill_holes;   // voxels that were never observed (count 0, background tsdf) may be corners
+	__device__ bool corner(size_t at, float& f) const
+	{
 		uint32_t c;
-		// a corner in a block that was never allocated makes the cube non-extractable (its edge owners have no storage)
-		if (!fetch(vox, nb, lx + d_corner[i][0], ly + d_corner[i][1], lz + d_corner[i][2], sdf_trunc, f, c)) return 0;
-		if ((!fill_holes && c == 0) || c < min_count) return 0;
-		fout[i] = f;
-		if (f < 0.0f) idx |= 1 << i;
+		unpack(vox[at], sdf_trunc, f, c);
+		return c >= min_count && (fill_holes || c != 0);
 	}
-	return idx == 255 ? 0 : idx;
-}
+	// vdbfusion: half_voxel_length + voxel_length * index
+	__device__ float centre(int idx) const { return voxel * 0.5f + voxel * (float)idx; }
+};
 
-// pass A: per voxel the cube case (u8) and, OR-ed into the owning voxels, which of their three edges carry a vertex.
-// One workgroup per occupied block, one thread per voxel.  flags / cases are indexed by COMPACT block index;
-// cidx maps hash slot -> compact index.
-__global__ __launch_bounds__(512) void mc_classify_kernel(const unsigned long long* __restrict__ keys, uint64_t mask,
-                                                          const unsigned long long* __restrict__ vox, const uint32_t* __restrict__ blocks,
-                                                          const uint32_t* __restrict__ cidx, float sdf_trunc, uint32_t min_count,
-                                                          int fill_holes, uint8_t* __restrict__ cases, uint32_t* __restrict__ flags)
-{
-	__shared__ int64_t s_nb[8];
-	const uint32_t slot = blocks[blockIdx.x];
-	if (threadIdx.x < 8) {
-		int bx, by, bz;
-		tsdf_decode_key(keys[slot], bx, by, bz);
-		s_nb[threadIdx.x] = threadIdx.x == 0 ? (int64_t)slot
-		                                     : tsdf_find_slot(keys, mask, tsdf_block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
-	}
-	__syncthreads();
-	const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
-	float f[8];
-	const int cs = cube_case(vox, s_nb, lx, ly, lz, sdf_trunc, min_count, fill_holes, f);
-	cases[(size_t)blockIdx.x * BLOCK_VOX + threadIdx.x] = (uint8_t)cs;
-	if (cs == 0) return;
-	const uint32_t em = d_edge_mask[cs];
-	for (int e = 0; e < 12; e++) {
-		if (!((em >> e) & 1)) continue;
-		const int o = d_edge_owner[e];
-		const int ox = lx + d_corner[o][0], oy = ly + d_corner[o][1], oz = lz + d_corner[o][2];
-		const int64_t s = s_nb[((oz >> 3) << 2) | ((oy >> 3) << 1) | (ox >> 3)];   // present: the cube was extractable
-		const uint32_t cb = cidx[s];
-		atomicOr(&flags[(size_t)cb * BLOCK_VOX + (((oz & 7) << 6) | ((oy & 7) << 3) | (ox & 7))], 1u << d_edge_axis[e]);
-	}
-}
-
-// pass B: per block totals (vertices, triangles) for the host-side exclusive scan
+// count: per block totals (vertices, triangles) for the host-side exclusive scan
 __global__ __launch_bounds__(512) void mc_count_kernel(const uint8_t* __restrict__ cases, const uint32_t* __restrict__ flags,
                                                        uint32_t* __restrict__ block_nv, uint32_t* __restrict__ block_nt)
 {
 	__shared__ uint32_t s_v[8], s_t[8];
 	const size_t i = (size_t)blockIdx.x * BLOCK_VOX + threadIdx.x;
-	uint32_t nv = __popc(flags[i] & 7u), nt = d_ntris[cases[i]];
+	uint32_t nv = __popc(flags[i] & 7u), nt = gsr_mc_ntris[cases[i]];
 	for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor((int)nv, o, 64); nt += __shfl_xor((int)nt, o, 64); }
 	if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = nv; s_t[threadIdx.x >> 6] = nt; }
 	__syncthreads();
@@ -325,70 +271,7 @@ __global__ __launch_bounds__(512) void mc_count_kernel(const uint8_t* __restrict
 	}
 }
 
-// exclusive scan of a per-voxel count inside a 512-thread block; returns this thread's offset
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w)
-{
-	uint32_t incl = v;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t t = (uint32_t)__shfl_up((int)incl, o, 64);
-		if (lane >= o) incl += t;
-	}
-	if (lane == 63) s_w[wv] = incl;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wv; w++) base += s_w[w];
-	__syncthreads();
-	return base + incl - v;
-}
-
-// pass C: vertices.  vbase[voxel] = index of the voxel's first vertex.
-__global__ __launch_bounds__(512) void mc_vertices_kernel(const unsigned long long* __restrict__ keys, uint64_t mask,
-                                                          const unsigned long long* __restrict__ vox, const uint32_t* __restrict__ blocks,
-                                                          const uint32_t* __restrict__ flags, const uint32_t* __restrict__ block_voff,
-                                                          float voxel_size, float sdf_trunc, uint32_t* __restrict__ vbase,
-                                                          float* __restrict__ vertices)
-{
-	__shared__ int64_t s_nb[8];
-	__shared__ uint32_t s_w[8];
-	__shared__ int s_b[3];
-	const uint32_t slot = blocks[blockIdx.x];
-	if (threadIdx.x < 8) {
-		int bx, by, bz;
-		tsdf_decode_key(keys[slot], bx, by, bz);
-		if (threadIdx.x == 0) { s_b[0] = bx; s_b[1] = by; s_b[2] = bz; }
-		s_nb[threadIdx.x] = threadIdx.x == 0 ? (int64_t)slot
-		                                     : tsdf_find_slot(keys, mask, tsdf_block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
-	}
-	__syncthreads();
-	const size_t i = (size_t)blockIdx.x * BLOCK_VOX + threadIdx.x;
-	const uint32_t fl = flags[i] & 7u;
-	const uint32_t off = block_voff[blockIdx.x] + block_excl_scan(__popc(fl), s_w);
-	vbase[i] = off;
-	if (!fl) return;
-	const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
-	float f0;
-	uint32_t c0;
-	fetch(vox, s_nb, lx, ly, lz, sdf_trunc, f0, c0);
-	// voxel centre in world units (vdbfusion: half_voxel_length + voxel_length * index)
-	const float half = voxel_size * 0.5f;
-	const float base[3] = {half + voxel_size * (float)(s_b[0] * 8 + lx), half + voxel_size * (float)(s_b[1] * 8 + ly),
-	                       half + voxel_size * (float)(s_b[2] * 8 + lz)};
-	uint32_t k = off;
-	for (int a = 0; a < 3; a++) {
-		if (!((fl >> a) & 1)) continue;
-		float f1;
-		uint32_t c1;
-		fetch(vox, s_nb, lx + (a == 0), ly + (a == 1), lz + (a == 2), sdf_trunc, f1, c1);
-		const float a0 = fabsf(f0), a1 = fabsf(f1);
-		float p[3] = {base[0], base[1], base[2]};
-		p[a] += a0 * voxel_size / (a0 + a1);
-		vertices[3 * (size_t)k] = p[0]; vertices[3 * (size_t)k + 1] = p[1]; vertices[3 * (size_t)k + 2] = p[2];
-		k++;
-	}
-}
-
-// pass D: triangles (vertex indices through the owners' vbase)
+// triangles (vertex indices through the owners' vbase)
 __global__ __launch_bounds__(512) void mc_triangles_kernel(const unsigned long long* __restrict__ keys, uint64_t mask,
                                                            const uint32_t* __restrict__ blocks, const uint32_t* __restrict__ cidx,
                                                            const uint8_t* __restrict__ cases, const uint32_t* __restrict__ flags,
@@ -397,25 +280,18 @@ __global__ __launch_bounds__(512) void mc_triangles_kernel(const unsigned long l
 {
 	__shared__ int64_t s_nb[8];
 	__shared__ uint32_t s_w[8];
-	const uint32_t slot = blocks[blockIdx.x];
-	if (threadIdx.x < 8) {
-		int bx, by, bz;
-		tsdf_decode_key(keys[slot], bx, by, bz);
-		s_nb[threadIdx.x] = threadIdx.x == 0 ? (int64_t)slot
-		                                     : tsdf_find_slot(keys, mask, tsdf_block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
-	}
-	__syncthreads();
+	gsr::neighbour_slots(keys, mask, blocks[blockIdx.x], s_nb, nullptr);
 	const size_t i = (size_t)blockIdx.x * BLOCK_VOX + threadIdx.x;
 	const int cs = cases[i];
-	const uint32_t nt = d_ntris[cs];
-	uint32_t t = block_toff[blockIdx.x] + block_excl_scan(nt, s_w);
+	const uint32_t nt = gsr_mc_ntris[cs];
+	uint32_t t = block_toff[blockIdx.x] + gsr::block_excl_scan(nt, s_w);
 	if (!nt) return;
 	const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
 	for (uint32_t k = 0; k < nt; k++, t++) {
 		for (int c = 0; c < 3; c++) {
-			const int e = d_tris[cs][3 * k + c];
-			const int o = d_edge_owner[e], ax = d_edge_axis[e];
-			const int ox = lx + d_corner[o][0], oy = ly + d_corner[o][1], oz = lz + d_corner[o][2];
+			const int e = gsr_mc_tris[cs][3 * k + c];
+			const int o = gsr_mc_edge_owner[e], ax = gsr_mc_edge_axis[e];
+			const int ox = lx + gsr_mc_corner[o][0], oy = ly + gsr_mc_corner[o][1], oz = lz + gsr_mc_corner[o][2];
 			const int64_t s = s_nb[((oz >> 3) << 2) | ((oy >> 3) << 1) | (ox >> 3)];
 			const size_t ov = (size_t)cidx[s] * BLOCK_VOX + (((oz & 7) << 6) | ((oy & 7) << 3) | (ox & 7));
 			const uint32_t fl = flags[ov] & 7u;
@@ -424,29 +300,12 @@ __global__ __launch_bounds__(512) void mc_triangles_kernel(const unsigned long l
 	}
 }
 
-bool g_tables_loaded[16] = {};
-int load_tables()
-{
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return GSR_ERR_HIP;
-	if (g_tables_loaded[dev]) return GSR_OK;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(d_ntris), gsr_mc_ntris, sizeof(gsr_mc_ntris)) != hipSuccess) return GSR_ERR_HIP;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(d_edge_mask), gsr_mc_edge_mask, sizeof(gsr_mc_edge_mask)) != hipSuccess) return GSR_ERR_HIP;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(d_tris), gsr_mc_tris, sizeof(gsr_mc_tris)) != hipSuccess) return GSR_ERR_HIP;
-	g_tables_loaded[dev] = true;
-	return GSR_OK;
-}
-
-bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
-
 }  // namespace
 
 namespace gsr {
 
 int launch_tsdf_mc_count(int num_blocks, const uint8_t* cases, const uint32_t* flags, uint32_t* block_nv, uint32_t* block_nt, hipStream_t s)
 {
-	const int rc = load_tables();
-	if (rc != GSR_OK) return rc;
 	hipLaunchKernelGGL(mc_count_kernel, dim3(num_blocks), dim3(512), 0, s, cases, flags, block_nv, block_nt);
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
@@ -455,8 +314,6 @@ int launch_tsdf_mc_triangles(const uint64_t* keys, uint64_t capacity, const uint
                              const uint8_t* cases, const uint32_t* flags, const uint32_t* vbase, const uint32_t* block_toff,
                              int* triangles, hipStream_t s)
 {
-	const int rc = load_tables();
-	if (rc != GSR_OK) return rc;
 	hipLaunchKernelGGL(mc_triangles_kernel, dim3(num_blocks), dim3(512), 0, s, reinterpret_cast<const unsigned long long*>(keys),
 	                   capacity - 1, blocks, cidx, cases, flags, vbase, block_toff, triangles);
 	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
@@ -518,18 +375,10 @@ int gsr_tsdf_mc_classify(const uint64_t* block_keys, uint64_t capacity, const ui
 	if (!block_keys || !voxels || !block_slots || !slot_to_block || !cases || !edge_flags || !block_num_vertices ||
 	    !block_num_triangles || !pow2(capacity))
 		return GSR_ERR_ARG;
-	const int rc = load_tables();
-	if (rc != GSR_OK) return rc;
-	hipStream_t s = (hipStream_t)stream;
-	// weights are integer counts here: weight < min_weight  <=>  count < ceil(min_weight)
-	const uint32_t min_count = min_weight <= 0.f ? 0u : (uint32_t)ceilf(min_weight);
-	if (hipMemsetAsync(edge_flags, 0, sizeof(uint32_t) * (size_t)num_blocks * BLOCK_VOX, s) != hipSuccess) return GSR_ERR_HIP;
-	hipLaunchKernelGGL(mc_classify_kernel, dim3(num_blocks), dim3(512), 0, s, reinterpret_cast<const unsigned long long*>(block_keys),
-	                   capacity - 1, reinterpret_cast<const unsigned long long*>(voxels), block_slots, slot_to_block, sdf_trunc,
-	                   min_count, fill_holes, cases, edge_flags);
-	hipLaunchKernelGGL(mc_count_kernel, dim3(num_blocks), dim3(512), 0, s, cases, edge_flags, block_num_vertices,
-	                   block_num_triangles);
-	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+	const PackedVoxels vol = {reinterpret_cast<const unsigned long long*>(voxels), 0.0f, sdf_trunc,
+	                          min_weight <= 0.f ? 0u : (uint32_t)ceilf(min_weight), fill_holes};
+	return gsr::launch_block_mc_classify(vol, block_keys, capacity, block_slots, num_blocks, slot_to_block, cases, edge_flags,
+	                                     block_num_vertices, block_num_triangles, (hipStream_t)stream);
 }
 
 int gsr_tsdf_mc_emit(const uint64_t* block_keys, uint64_t capacity, const uint64_t* voxels, const uint32_t* block_slots,
@@ -541,15 +390,9 @@ int gsr_tsdf_mc_emit(const uint64_t* block_keys, uint64_t capacity, const uint64
 	if (!block_keys || !voxels || !block_slots || !slot_to_block || !cases || !edge_flags || !block_vertex_offset ||
 	    !block_triangle_offset || !vertex_base || !vertices || !triangles || !pow2(capacity))
 		return GSR_ERR_ARG;
-	const int rc = load_tables();
-	if (rc != GSR_OK) return rc;
-	hipStream_t s = (hipStream_t)stream;
-	hipLaunchKernelGGL(mc_vertices_kernel, dim3(num_blocks), dim3(512), 0, s, reinterpret_cast<const unsigned long long*>(block_keys),
-	                   capacity - 1, reinterpret_cast<const unsigned long long*>(voxels), block_slots, edge_flags,
-	                   block_vertex_offset, voxel_size, sdf_trunc, vertex_base, vertices);
-	hipLaunchKernelGGL(mc_triangles_kernel, dim3(num_blocks), dim3(512), 0, s, reinterpret_cast<const unsigned long long*>(block_keys),
-	                   capacity - 1, block_slots, slot_to_block, cases, edge_flags, vertex_base, block_triangle_offset, triangles);
-	return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+	const PackedVoxels vol = {reinterpret_cast<const unsigned long long*>(voxels), voxel_size, sdf_trunc, 0u, 0};
+	return gsr::launch_block_mc_emit(vol, block_keys, capacity, block_slots, num_blocks, slot_to_block, cases, edge_flags, block_vertex_offset,
+	                                 block_triangle_offset, vertex_base, vertices, nullptr, triangles, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -10,29 +10,30 @@
 // voxel of every block the frame's depth touches projects into the depth image and keeps a running average.
 //
 // MI355X design:
-//   * the block hash and 64-bit keys of gsr_tsdf.hip (gsr_internal.h), a block's voxels AT its hash slot;
+//   * the block hash and 64-bit keys of gsr_tsdf.hip (gsr_block_volume.h), a block's voxels AT its hash slot;
 //   * voxels are SoA per block: five planes of 512 f32 -- tsdf, weight, r, g, b -- so a wave (one z-slice of 8 x 8
 //     voxels, x fastest) reads and writes whole 256-byte lines, and its 64 voxel centres project to a compact footprint
 //     of the depth image;
 //   * touch (one thread per strided depth pixel) inserts the blocks of the pixel's +-sdf_trunc box and stamps their slots
 //     with the frame number; integrate runs one workgroup per stamped slot.  One voxel is written by one thread in one
 //     frame: float running averages, no atomics, deterministic;
-//   * the matrices and intrinsics travel by value in the kernel argument block (scalar registers).
+//   * the matrices and intrinsics travel by value in the kernel argument block (scalar registers);
+//   * extraction: the block marching cubes of gsr_block_volume.h with the float planes as its voxel format (PlaneVoxels): this
+//     file has no marching-cubes kernel of its own.
 // Plain float arithmetic, one rounding per operation (the library is compiled with -ffp-contract=off and correctly
 // rounded divide / sqrt): the device results equal the model's bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gsrast.h"
-#include "gsr_internal.h"
-#include "gsr_mc_tables.h"
+#include "gsr_block_volume.h"
 
 namespace {
 
+using gsr::pow2;
 using gsr::tsdf_block_key;
 using gsr::tsdf_decode_key;
 using gsr::tsdf_find_or_insert;
-using gsr::tsdf_find_slot;
 
 constexpr int BLOCK_VOX = gsr::TSDF_BLOCK_VOX;
 constexpr int PLANES = 5;                        // tsdf, weight, r, g, b
@@ -40,11 +41,6 @@ constexpr int BLOCK_F32 = PLANES * BLOCK_VOX;    // floats per hash slot (10 KiB
 
 struct Mat34 { float m[12]; };                   // rows 0..2 of a rigid 4x4, row-major
 struct Pinhole { float fx, fy, cx, cy; };
-
-__device__ __constant__ uint16_t d_edge_mask[256];
-__device__ __constant__ int d_corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
-__device__ __constant__ uint8_t d_edge_owner[12] = {0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3};
-__device__ __constant__ uint8_t d_edge_axis[12] = {0, 1, 0, 1, 0, 1, 0, 1, 2, 2, 2, 2};
 
 // row r of M (x, y, z, 1), summed left to right
 __device__ __forceinline__ float xform(const Mat34& M, int r, float x, float y, float z)
@@ -179,130 +175,27 @@ __global__ __launch_bounds__(512) void ctsdf_export_kernel(const float* __restri
 	for (int c = 0; c < 3; c++) color[3 * dst + c] = cell[(2 + c) * BLOCK_VOX];
 }
 
-// ---- marching cubes over the occupied blocks: the two-pass indexed scheme of gsr_tsdf.hip reading the float planes ----
-// s_nb[8]: hash slots of the 2x2x2 blocks starting at the workgroup's block (-1 = absent), index dz*4+dy*2+dx
-__device__ __forceinline__ void neighbour_slots(const unsigned long long* __restrict__ keys, uint64_t mask, uint32_t slot, int64_t* s_nb,
-                                                int* s_b)
-{
-	if (threadIdx.x < 8) {
-		int bx, by, bz;
-		tsdf_decode_key(keys[slot], bx, by, bz);
-		if (threadIdx.x == 0 && s_b) { s_b[0] = bx; s_b[1] = by; s_b[2] = bz; }
-		s_nb[threadIdx.x] = threadIdx.x == 0 ? (int64_t)slot
-		                                     : tsdf_find_slot(keys, mask, tsdf_block_key(bx + (threadIdx.x & 1), by + ((threadIdx.x >> 1) & 1), bz + (threadIdx.x >> 2)));
+// ---- marching cubes over the occupied blocks: the float planes as a voxel format of the scheme of gsr_block_volume.h ----
+// A cube is meshed iff all 8 corners have weight > 0 and weight >= min_weight.  A vertex's colour is c0 + r (c1 - c0) between
+// the two voxels of its edge, kept inside [min, max] of the two, / 255.
+struct PlaneVoxels {
+	static constexpr int SLOT_ELEMS = BLOCK_F32;
+	static constexpr bool COLORS = true;
+	const float* vox;
+	float voxel, min_weight;
+	__device__ bool corner(size_t at, float& f) const
+	{
+		const float w = vox[at + BLOCK_VOX];
+		f = vox[at];
+		return w > 0.0f && !(w < min_weight);
 	}
-	__syncthreads();
-}
-
-// address of the voxel at local coordinates (lx,ly,lz) in [0,8] of the 2x2x2 block neighbourhood; nullptr = block absent
-__device__ __forceinline__ const float* voxel_at(const float* __restrict__ vox, const int64_t* nb, int lx, int ly, int lz)
-{
-	const int64_t s = nb[((lz >> 3) << 2) | ((ly >> 3) << 1) | (lx >> 3)];
-	return s < 0 ? nullptr : vox + (size_t)s * BLOCK_F32 + (((lz & 7) << 6) | ((ly & 7) << 3) | (lx & 7));
-}
-
-// pass A: per voxel the cube case and, OR-ed into the owning voxels, which of their three edges carry a vertex.
-// A cube is meshed iff all 8 corners have weight > 0 and weight >= min_weight; a corner is inside iff tsdf < 0.
-__global__ __launch_bounds__(512) void ctsdf_mc_classify_kernel(const unsigned long long* __restrict__ keys, uint64_t mask,
-                                                                const float* __restrict__ vox, const uint32_t* __restrict__ blocks,
-                                                                const uint32_t* __restrict__ cidx, float min_weight,
-                                                                uint8_t* __restrict__ cases, uint32_t* __restrict__ flags)
-{
-	__shared__ int64_t s_nb[8];
-	neighbour_slots(keys, mask, blocks[blockIdx.x], s_nb, nullptr);
-	const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
-	int cs = 0;
-	bool ok = true;
-#pragma unroll
-	for (int i = 0; i < 8; i++) {
-		const float* c = voxel_at(vox, s_nb, lx + d_corner[i][0], ly + d_corner[i][1], lz + d_corner[i][2]);
-		if (!c) { ok = false; break; }
-		const float w = c[BLOCK_VOX];
-		if (!(w > 0.0f) || w < min_weight) { ok = false; break; }
-		if (c[0] < 0.0f) cs |= 1 << i;
+	__device__ float centre(int idx) const { return ((float)idx + 0.5f) * voxel; }
+	__device__ float colour(size_t at0, size_t at1, int c, float r) const
+	{
+		const float q0 = vox[at0 + (2 + c) * BLOCK_VOX], q1 = vox[at1 + (2 + c) * BLOCK_VOX];
+		return fminf(fmaxf(q0 + r * (q1 - q0), fminf(q0, q1)), fmaxf(q0, q1)) / 255.0f;
 	}
-	if (!ok || cs == 255) cs = 0;
-	cases[(size_t)blockIdx.x * BLOCK_VOX + threadIdx.x] = (uint8_t)cs;
-	if (cs == 0) return;
-	const uint32_t em = d_edge_mask[cs];
-	for (int e = 0; e < 12; e++) {
-		if (!((em >> e) & 1)) continue;
-		const int o = d_edge_owner[e];
-		const int ox = lx + d_corner[o][0], oy = ly + d_corner[o][1], oz = lz + d_corner[o][2];
-		const int64_t s = s_nb[((oz >> 3) << 2) | ((oy >> 3) << 1) | (ox >> 3)];   // present: the cube was extractable
-		atomicOr(&flags[(size_t)cidx[s] * BLOCK_VOX + (((oz & 7) << 6) | ((oy & 7) << 3) | (ox & 7))], 1u << d_edge_axis[e]);
-	}
-}
-
-// exclusive scan of a per-voxel count inside a 512-thread block; returns this thread's offset
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w)
-{
-	uint32_t incl = v;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t t = (uint32_t)__shfl_up((int)incl, o, 64);
-		if (lane >= o) incl += t;
-	}
-	if (lane == 63) s_w[wv] = incl;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wv; w++) base += s_w[w];
-	return base + incl - v;
-}
-
-// vertices and their colours.  A vertex lies at the linear zero crossing between the two voxel centres of its edge:
-// r = |f0| / (|f0| + |f1|) from the owning voxel; its colour is c0 + r (c1 - c0), kept inside [min, max] of the two, / 255.
-__global__ __launch_bounds__(512) void ctsdf_mc_vertices_kernel(const unsigned long long* __restrict__ keys, uint64_t mask,
-                                                                const float* __restrict__ vox, const uint32_t* __restrict__ blocks,
-                                                                const uint32_t* __restrict__ flags, const uint32_t* __restrict__ block_voff,
-                                                                float voxel_length, uint32_t* __restrict__ vbase,
-                                                                float* __restrict__ vertices, float* __restrict__ colors)
-{
-	__shared__ int64_t s_nb[8];
-	__shared__ uint32_t s_w[8];
-	__shared__ int s_b[3];
-	neighbour_slots(keys, mask, blocks[blockIdx.x], s_nb, s_b);
-	const size_t i = (size_t)blockIdx.x * BLOCK_VOX + threadIdx.x;
-	const uint32_t fl = flags[i] & 7u;
-	const uint32_t off = block_voff[blockIdx.x] + block_excl_scan(__popc(fl), s_w);
-	vbase[i] = off;
-	if (!fl) return;
-	const int lx = threadIdx.x & 7, ly = (threadIdx.x >> 3) & 7, lz = threadIdx.x >> 6;
-	const float* c0 = voxel_at(vox, s_nb, lx, ly, lz);
-	const float f0 = c0[0];
-	const float base[3] = {((float)(s_b[0] * 8 + lx) + 0.5f) * voxel_length, ((float)(s_b[1] * 8 + ly) + 0.5f) * voxel_length,
-	                       ((float)(s_b[2] * 8 + lz) + 0.5f) * voxel_length};
-	uint32_t k = off;
-	for (int a = 0; a < 3; a++) {
-		if (!((fl >> a) & 1)) continue;
-		const float* c1 = voxel_at(vox, s_nb, lx + (a == 0), ly + (a == 1), lz + (a == 2));   // present: an extractable cube flagged the edge
-		const float a0 = fabsf(f0), a1 = fabsf(c1[0]);
-		float p[3] = {base[0], base[1], base[2]};
-		p[a] += a0 * voxel_length / (a0 + a1);
-		const float r = a0 / (a0 + a1);
-#pragma unroll
-		for (int c = 0; c < 3; c++) {
-			vertices[3 * (size_t)k + c] = p[c];
-			const float q0 = c0[(2 + c) * BLOCK_VOX], q1 = c1[(2 + c) * BLOCK_VOX];
-			const float q = fminf(fmaxf(q0 + r * (q1 - q0), fminf(q0, q1)), fmaxf(q0, q1));
-			colors[3 * (size_t)k + c] = q / 255.0f;
-		}
-		k++;
-	}
-}
-
-bool g_tables_loaded[16] = {};
-int load_tables()
-{
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return GSR_ERR_HIP;
-	if (g_tables_loaded[dev]) return GSR_OK;
-	if (hipMemcpyToSymbol(HIP_SYMBOL(d_edge_mask), gsr_mc_edge_mask, sizeof(gsr_mc_edge_mask)) != hipSuccess) return GSR_ERR_HIP;
-	g_tables_loaded[dev] = true;
-	return GSR_OK;
-}
-
-bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
+};
 
 bool rigid_ok(const float* m)
 {
@@ -369,14 +262,9 @@ int gsr_ctsdf_mc_classify(const uint64_t* block_keys, uint64_t capacity, const f
 	if (!block_keys || !voxels || !block_slots || !slot_to_block || !cases || !edge_flags || !block_num_vertices || !block_num_triangles ||
 	    !pow2(capacity))
 		return GSR_ERR_ARG;
-	const int rc = load_tables();
-	if (rc != GSR_OK) return rc;
-	hipStream_t s = (hipStream_t)stream;
-	if (hipMemsetAsync(edge_flags, 0, sizeof(uint32_t) * (size_t)num_blocks * BLOCK_VOX, s) != hipSuccess) return GSR_ERR_HIP;
-	hipLaunchKernelGGL(ctsdf_mc_classify_kernel, dim3(num_blocks), dim3(512), 0, s, reinterpret_cast<const unsigned long long*>(block_keys),
-	                   capacity - 1, voxels, block_slots, slot_to_block, min_weight, cases, edge_flags);
-	if (hipGetLastError() != hipSuccess) return GSR_ERR_HIP;
-	return gsr::launch_tsdf_mc_count(num_blocks, cases, edge_flags, block_num_vertices, block_num_triangles, s);
+	const PlaneVoxels vol = {voxels, 0.0f, min_weight};
+	return gsr::launch_block_mc_classify(vol, block_keys, capacity, block_slots, num_blocks, slot_to_block, cases, edge_flags,
+	                                     block_num_vertices, block_num_triangles, (hipStream_t)stream);
 }
 
 int gsr_ctsdf_mc_emit(const uint64_t* block_keys, uint64_t capacity, const float* voxels, const uint32_t* block_slots, int num_blocks,
@@ -388,12 +276,9 @@ int gsr_ctsdf_mc_emit(const uint64_t* block_keys, uint64_t capacity, const float
 	if (!block_keys || !voxels || !block_slots || !slot_to_block || !cases || !edge_flags || !block_vertex_offset || !block_triangle_offset ||
 	    !vertex_base || !vertices || !colors || !triangles || !pow2(capacity))
 		return GSR_ERR_ARG;
-	hipStream_t s = (hipStream_t)stream;
-	hipLaunchKernelGGL(ctsdf_mc_vertices_kernel, dim3(num_blocks), dim3(512), 0, s, reinterpret_cast<const unsigned long long*>(block_keys),
-	                   capacity - 1, voxels, block_slots, edge_flags, block_vertex_offset, voxel_length, vertex_base, vertices, colors);
-	if (hipGetLastError() != hipSuccess) return GSR_ERR_HIP;
-	return gsr::launch_tsdf_mc_triangles(block_keys, capacity, block_slots, num_blocks, slot_to_block, cases, edge_flags, vertex_base,
-	                                     block_triangle_offset, triangles, s);
+	const PlaneVoxels vol = {voxels, voxel_length, 0.0f};
+	return gsr::launch_block_mc_emit(vol, block_keys, capacity, block_slots, num_blocks, slot_to_block, cases, edge_flags, block_vertex_offset,
+	                                 block_triangle_offset, vertex_base, vertices, colors, triangles, (hipStream_t)stream);
 }
 
 }  // extern "C"

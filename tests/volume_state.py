@@ -2,7 +2,7 @@
 
 Two things live here:
 
-  * the block hash of the sparse volumes restated on the host (csrc/gsr_internal.h: key = three block coordinates, each biased
+  * the block hash of the sparse volumes restated on the host (csrc/gsr_block_volume.h: key = three block coordinates, each biased
     by 2^20, in 21-bit fields; empty = all bits set; home slot = mix64(key) & (capacity - 1); linear probing), so that a test
     can WRITE a volume's state -- block keys and voxel words / planes -- instead of reaching it through integrate().  A
     written state holds what no scan of a smooth surface produces: every marching-cubes case, exact zeros, holes, an

@@ -519,6 +519,9 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) void composite_bwd_kernel(
 //     plane turn  read2_b32 + read_b32 + write2_b32 + write_b32      4 + 2 + 6 + 4 = 16     unchanged     16
 //     per group of 4 steps: list word (b32), centre (b64), two slab reads (b128)  12 -> 3   unchanged      3
 //                                                                           about 45                 about 35
+//   Since round 10 the list word is a ds_read_b64 (four 16-bit entries; 2 cycles, as before), and the exact modes read the phase-2
+//   lane's entry once more (ds_read_u16, 2 cycles per group).  The workgroup's LDS is 40 256 B: the lists are 4 352 B of it (16 lists
+//   of 136 entries of 2 B; 2 176 B until round 10) -- four workgroups per CU, 161 024 of 163 840 B.
 //   The ten words a step needs were three parts of 16 B in the layout of GsRec, of which the compiler read 16 + 12 + 12; they are
 //   regrouped at staging (sA / sB / sC below) so that the step reads 16 + 16 + 8 (the exact modes 16 + 16 + 16: pcut rides in sC.z).
 //   Never read 12 bytes from LDS in a loop.  What is left is led by the plane turn (16 of 35).  The "one float4 per lane and turn"
@@ -534,8 +537,12 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) void composite_bwd_kernel(
                              // once per round -- census at C3: 30.1 k workgroup steps at 64, 28.3 k at 128 (20.9 k ideal)
 #endif
 #define GSR_BWQ_HALVES ((GSR_BWQ_BATCH + 63) / 64)
-#define GSR_BWQ_LIST (GSR_BWQ_BATCH + 8)   // bytes per quarter list: the entries + 8 sentinels
+#define GSR_BWQ_LIST (GSR_BWQ_BATCH + 8)   // 16-bit entries per quarter list: the hits + 8 sentinels
 #define GSR_BWQ_SENT GSR_BWQ_BATCH         // batch index of the sentinel record (opacity 0)
+// A list entry is the instance's batch index times 16: the byte offset of its record in sA / sB / sC, which a step adds to the
+// arrays' bases as it is (round 10; until then the list held the index in a byte, and every step shifted it)
+#define GSR_BWQ_ENTRY(j) ((uint32_t)(j) << 4)
+template <bool B> struct GsBool { static constexpr bool value = B; };
 // s_waitcnt vmcnt(0) alone (expcnt 7, lgkmcnt 15 = no wait; gfx9 encoding): every outstanding global load has arrived.  As a builtin it
 // is seen by the compiler's own wait insertion, which counts from it
 #define GSR_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0F70)
@@ -570,7 +577,7 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 	__shared__ uint16_t s_qmask[GSR_BWQ_BATCH];   // the forward's block masks of the staged instances (when it left them)
 	__shared__ __attribute__((aligned(16))) float s_plane[4][GSR_BWQ_BATCH * GSR_PLANE_STRIDE];
 	__shared__ __attribute__((aligned(16))) float2 s_slab[4][4 * GSR_BWQ_QSTRIDE];
-	__shared__ __attribute__((aligned(16))) uint8_t s_list[4][4][GSR_BWQ_LIST];
+	__shared__ __attribute__((aligned(16))) uint16_t s_list[4][4][GSR_BWQ_LIST];   // GSR_BWQ_ENTRY of the hits, per wave and quarter
 	__shared__ int s_max[4];
 	if (blockIdx.x == 0 && threadIdx.x == 0 && bgv.flag_dst != nullptr) *bgv.flag_dst = bgv.flag;   // regime word (GsBg)
 	// XCD-banded static order, or (skewed frames) longest walk first: launch_tile_order
@@ -582,7 +589,9 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 	if ((!bgv.tile_order && ((int)(blockIdx.x >> 3) >= chunk || local >= tb_n)) || tile >= T) return;
 	if ((uint32_t)tile < bgv.tile_lo || (uint32_t)tile >= bgv.tile_hi) return;   // (longest-first order of a skewed frame: every tile is offered to both bands)
 	const int tid = threadIdx.x;
-	const int lane = tid & 63, wv = tid >> 6, qd = lane >> 4;
+	// (the wave's index as a scalar: what is derived from it alone -- the block's origin, the wave's slab, plane and lists -- then
+	// lives in scalar registers, of which there are enough, and not in vector registers, of which there are none to spare)
+	const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), qd = lane >> 4;
 	TM_DECL
 	const int tx = tile % gx, ty = tile / gx;
 	// lane -> pixel as in composite_fwd_quarter_kernel: quarter qd of wave wv is one 4x4 block
@@ -728,7 +737,12 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 	}
 	GSR_WAIT_VM0();   // the first round stages at once; and the round loop is entered, as it is re-entered, with no load in flight
 	TM(2)
-	const uint8_t* my_list = &s_list[wv][qd][0];
+	const uint16_t* my_list = &s_list[wv][qd][0];
+	// `contributor` of entry j is pos = top - 1 - j, and the pixel takes it when pos < lc (backward.cu:520-524).  For integer j that is
+	// j > top - 1 - lc, and 16 j > 16 (top - 1 - lc): one compare of the list entry as it is with a threshold that moves by a batch
+	// per round -- the same boolean for every entry, the sentinel included (its all-zero record fails the alpha test whatever this
+	// says).  Beyond the round (lc >= top) the threshold is negative and every entry passes; before it, it is at least 16 * 127
+	int thr16 = (bmax - 1 - lc) * 16;
 	const char* recA = reinterpret_cast<const char*>(sA);
 	const char* recB = reinterpret_cast<const char*>(sB);
 	const char* recC = reinterpret_cast<const char*>(sC);
@@ -772,14 +786,14 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 		// (the two constants are made here, opaque to the compiler: as loop invariants it keeps them -- eight registers
 		// of a 128-bit zero and a 128-bit sentinel word -- alive across the walk, which the prefetched records then pay for in spills)
 		float zero = 0.f;
-		uint32_t ss = GSR_BWQ_SENT * 0x01010101u;
+		uint32_t ss = GSR_BWQ_ENTRY(GSR_BWQ_SENT) * 0x00010001u;
 		asm volatile("" : "+v"(zero), "+v"(ss));
 		for (int i = tid; i < 4 * GSR_BWQ_BATCH * GSR_PLANE_STRIDE / 4; i += GSR_BWD_THREADS)
 			reinterpret_cast<float4*>(&s_plane[0][0])[i] = make_float4(zero, zero, zero, zero);
-		// this wave's four lists: sentinels, then (below) the hits of each quarter in list order
-		if (lane < 4 * GSR_BWQ_LIST / 16) {
-			reinterpret_cast<uint4*>(&s_list[wv][0][0])[lane] = make_uint4(ss, ss, ss, ss);
-		}
+		// this wave's four lists: sentinels, then (below) the hits of each quarter in list order (68 stores of 16 B: a second trip for four lanes)
+		static_assert((4 * GSR_BWQ_LIST * sizeof(uint16_t)) % 16 == 0, "a wave's lists are filled 16 B at a time");
+		for (int i = lane; i < (int)(4 * GSR_BWQ_LIST * sizeof(uint16_t) / 16); i += 64)
+			reinterpret_cast<uint4*>(&s_list[wv][0][0])[i] = make_uint4(ss, ss, ss, ss);
 		TM(6)
 		__syncthreads();
 		TM(7)
@@ -795,7 +809,7 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 		const bool h_ = (mk >> (QQ)) & 1u;                                                                           \
 		const unsigned long long bm = __ballot(h_);                                                                  \
 		const int pos_ = CNT + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)); \
-		if (h_) s_list[wv][QQ][pos_] = (uint8_t)jl;                                                                  \
+		if (h_) s_list[wv][QQ][pos_] = (uint16_t)GSR_BWQ_ENTRY(jl);                                                  \
 		CNT += __popcll(bm);                                                                                         \
 	}
 #pragma unroll
@@ -828,25 +842,28 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 		// one list step of every quarter: (q, w) of the lane's pixel for the quarter's entry, into slab row `st`
 		// 16 + 16 + 8 bytes (FX; the exact modes need pcut: 16 + 16 + 16).  Never 12: a 96-bit LDS read costs two 128-bit ones
 		struct Rec { float4 A, B; float2 C; float pcut; };
-		auto fetch = [&](const uint32_t j) -> Rec {
+		auto fetch = [&](const uint32_t e) -> Rec {   // e: the list entry, GSR_BWQ_ENTRY(j)
 			Rec r;
-			r.A = *reinterpret_cast<const float4*>(recA + j * 16);
-			r.B = *reinterpret_cast<const float4*>(recB + j * 16);
+			r.A = *reinterpret_cast<const float4*>(recA + e);
+			r.B = *reinterpret_cast<const float4*>(recB + e);
 			if (FX) {
-				r.C = *reinterpret_cast<const float2*>(recC + j * 16);
+				r.C = *reinterpret_cast<const float2*>(recC + e);
 				r.pcut = 0.f;
 			} else {
-				float4 c = *reinterpret_cast<const float4*>(recC + j * 16);
+				float4 c = *reinterpret_cast<const float4*>(recC + e);
 				asm volatile("" : "+v"(c.w));   // the spare word counts as used: the compiler must not narrow the read to 12 bytes
 				r.C = make_float2(c.x, c.y);
 				r.pcut = c.z;
 			}
 			return r;
 		};
-		auto step = [&](const Rec& rc, const uint32_t j, const int st) {
+		// BG (GsBool): the loop of a wave with a background term (any_bg) carries its two instructions unconditionally, the other
+		// loop neither them nor a test -- as a wave-uniform branch in every step it cost s_andn2 + s_cbranch per step and cut the
+		// step into blocks the scheduler does not move work across (round 10)
+		auto step = [&](const Rec& rc, const uint32_t e, const int st, auto BG) {
 			const float4 A = rc.A, B = rc.B;
 			const float3 Cc = make_float3(B.w, rc.C.x, rc.C.y);   // r, g, b
-			const int pos = top - 1 - (int)j;   // == `contributor` after decrement (backward.cu:520)
+			const bool in_front = (int)e > thr16;   // `contributor` after decrement (backward.cu:520) < last_contributor: see thr16
 			const float dx = A.x - pixfx, dy = A.y - pixfy;
 			const float power = FMA(A.w * dx, dy, FMA(B.x * dy, dy, (A.z * dx) * dx));
 			float G, a0;
@@ -854,13 +871,13 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			if (!FX) {
 				G = gs_exp(power);
 				a0 = B.y * G;
-				live = (pos < lc) & (power <= 0.0f) & (power >= rc.pcut) & (!(a0 < 1.0f / 255.0f));
+				live = in_front & (power <= 0.0f) & (power >= rc.pcut) & (!(a0 < 1.0f / 255.0f));
 			} else {
 				// gs_exp_hw is valid for every power <= 0, and power < pcut implies opacity * exp(power) < (1/255) exp(-1e-3):
 				// the forward's pcut pre-test is implied by the alpha test
 				G = gs_exp_hw(power);
 				a0 = B.y * G;
-				live = (pos < lc) & (power <= 0.0f) & (!(a0 < 1.0f / 255.0f));
+				live = in_front & (power <= 0.0f) & (!(a0 < 1.0f / 255.0f));
 			}
 			// a dead pixel (and the sentinel of an exhausted quarter) is carried through with G masked to 0: alpha = 0,
 			// 1/(1-alpha) = 1 (gsr_selftest), w = 0, q = 0, S <- fma(0, ., S)
@@ -872,17 +889,12 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			const float cd = FMA(Cc.x, dLp0, FMA(Cc.y, dLp1, FMA(Cc.z, dLp2, CONLY ? 0.f : FMA(B.z, dLd, dLo))));   // CONLY: dLd = dLo = 0, depth >= 0: that FMA is +0
 			const float diff = cd - S;
 			float dL_dalpha = diff * test_T;
-			if (any_bg) {                                                         // backward.cu:584-587
-				asm volatile("");
-				dL_dalpha = FMA(-(T_final * rinv), bg_dot, dL_dalpha);
-			}
+			if (decltype(BG)::value) dL_dalpha = FMA(-(T_final * rinv), bg_dot, dL_dalpha);   // backward.cu:584-587
 			const float q = Gm * dL_dalpha;
 			S = FMA(alpha, diff, S);
 			T_ = TSEL ? (live ? test_T : T_) : test_T;
 			my_slab_w[16 * st] = make_float2(q, w);
 		};
-		// four list entries per read, fetched one group ahead of their use; the scheduling barrier keeps the read up
-		// here (left alone, the scheduler sinks it to its use and exposes a full LDS latency per group)
 		// The sums of a (quarter, instance) go into the instance's slot of the wave's plane; quarters may meet in an
 		// instance, so the four quarters take turns (LDS float atomics would serialise every lane: measured 2x the
 		// kernel time): the results of one phase 2 stay pending and are added by quarter k around step k of the NEXT
@@ -905,35 +917,35 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 				if (!r2_hi) pn_dst[8] = t2 + pn2;
 			}
 		};
-		uint32_t pk = *reinterpret_cast<const uint32_t*>(my_list);
-		for (int i = 0; i < n; i += GSR_BWQ_U) {
-			const uint32_t cur = pk;
-			pk = *reinterpret_cast<const uint32_t*>(my_list + i + GSR_BWQ_U);
-			__builtin_amdgcn_sched_barrier(0);
-			// (requesting the record of step k + 1 before evaluating step k -- two alternating register sets, what bought
-			// 7 % in the per-wave kernel -- changes nothing here: measured 0.528 against 0.527 ms)
-			turn_read(0); step(fetch(cur & 0xffu), cur & 0xffu, 0); turn_write(0);
-			turn_read(1); step(fetch((cur >> 8) & 0xffu), (cur >> 8) & 0xffu, 1); turn_write(1);
-			turn_read(2); step(fetch((cur >> 16) & 0xffu), (cur >> 16) & 0xffu, 2); turn_write(2);
-			turn_read(3); step(fetch(cur >> 24), cur >> 24, 3); turn_write(3);
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			// ---- phase 2: lane = (quarter qd, step u2, pixel row r2) ----
+		// ---- phase 2: lane = (quarter qd, step u2, pixel row r2); `cur`: the group's four entries, i: its first list position ----
+		// the lane's entry is 16 bits out of the group's 64: one v_perm_b32 by a selector that never changes (bytes 2 u2 and 2 u2 + 1,
+		// two zeros).  The exact modes have no registers left to keep the group's 64 bits through the four steps (they spilled):
+		// there the lane reads its entry from the list again
+		const uint32_t sel2 = 0x0c0c0000u | ((2u * u2 + 1u) << 8) | (2u * u2);
+		auto phase2 = [&](const uint2 cur, const int i) {
 			{
 				const bool act = i + u2 < my_cnt;
-				const uint32_t j = act ? (cur >> (8 * u2)) & 0xffu : 0u;
-				const float2 ctr = *reinterpret_cast<const float2*>(recA + j * 16);
+				const uint32_t e = act ? (FX ? __builtin_amdgcn_perm(cur.y, cur.x, sel2) : (uint32_t)my_list[i + u2]) : 0u;
+				const float2 ctr = *reinterpret_cast<const float2*>(recA + e);
 				const float4 v01 = my_slab_r[0], v23 = my_slab_r[1];   // (q, w) of the row's four pixels
 				const float dy = ctr.y - y2, X = ctr.x - x2;
 				const float qv[4] = {v01.x, v01.z, v23.x, v23.z}, wv_[4] = {v01.y, v01.w, v23.y, v23.w};
-				float S0 = 0.f, a0 = 0.f, a2 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f, a8 = 0.f, a9 = 0.f;
+				// S0 and a0 start from the first pixel's value, not from 0 + it (the compiler has to keep that add: -0 + 0 = +0).  What
+				// can differ is the sign of a zero sum, when every q (or every q dx) of the row is a -0.  It does not reach memory:
+				// a0 and the products dy * S0, dy * a0, dy * a1 (zeros either way) go through the fold into t + pn onto a plane word
+				// that was zeroed to +0 or already holds a sum with a +0 in it, S0 into a5 = fma(..) + S0 likewise, and the flush
+				// adds the four planes ((p0 + p1) + p2) + p3: a -0 summand added to a +0 is +0, so no sign survives.  (Checked
+				// bit for bit against the round before, and by tests/test_gpu_backward_walk_lists.py on rows of zero gradients.)
+				float S0 = qv[0], a0 = qv[0] * X, a2 = FMA(a0, X, 0.f), a5 = 0.f, a6 = 0.f, a7 = 0.f, a8 = 0.f, a9 = 0.f;
 #pragma unroll
 				for (int sx = 0; sx < 4; sx++) {
 					const float dx = X - (float)sx;
-					const float t = qv[sx] * dx;
-					S0 += qv[sx];
-					a0 += t;
-					a2 = FMA(t, dx, a2);
+					if (sx > 0) {
+						const float t = qv[sx] * dx;
+						S0 += qv[sx];
+						a0 += t;
+						a2 = FMA(t, dx, a2);
+					}
 					if (!CONLY) a5 = FMA(wv_[sx], g_op[sx], a5);      // backward.cu:575 (+ :607 below: + sum q); CONLY: w * 0 added to +0 stays +0
 					a6 = FMA(wv_[sx], g_pix[sx].x, a6);
 					a7 = FMA(wv_[sx], g_pix[sx].y, a7);
@@ -943,26 +955,56 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 				a5 += S0;
 				float a1 = dy * S0, a3 = dy * a0;
 				float a4 = dy * a1;
-				// fold the four rows (lanes r2 = 0..3 of the same quarter and step): quad butterflies
-				GSR_DPP_ADD(a0, 0xB1); GSR_DPP_ADD(a1, 0xB1); GSR_DPP_ADD(a2, 0xB1); GSR_DPP_ADD(a3, 0xB1); GSR_DPP_ADD(a4, 0xB1);
-				GSR_DPP_ADD(a5, 0xB1);
-				GSR_DPP_ADD(a0, 0x4E); GSR_DPP_ADD(a1, 0x4E); GSR_DPP_ADD(a2, 0x4E); GSR_DPP_ADD(a3, 0x4E); GSR_DPP_ADD(a4, 0x4E);
-				GSR_DPP_ADD(a5, 0x4E);
+				// fold the four rows (lanes r2 = 0..3 of the same quarter and step) as a reduce-scatter: lane r2 stores sums r2 and
+				// (r2 < 2) 8 + r2 only, so it selects BEFORE it exchanges -- of a pair of sums the odd lane keeps the odd one and hands
+				// the even one to its neighbour (0xB1), then the upper lanes keep the pair (a2, a3) and hand (a0, a1) down (0x4E).
+				// Each lane adds what the full butterflies added for the sums it stores, in the same association (own pair sum +
+				// the other pair's): 13 instructions for 16 (12 adds, then 4 selects), the same bits
+				const bool lo1 = (r2 & 1) != 0;
+				const float b01 = (lo1 ? a1 : a0) + GSR_DPP_OF(lo1 ? a0 : a1, 0xB1);
+				const float b23 = (lo1 ? a3 : a2) + GSR_DPP_OF(lo1 ? a2 : a3, 0xB1);
+				const float b45 = (lo1 ? a5 : a4) + GSR_DPP_OF(lo1 ? a4 : a5, 0xB1);
 				// the four colour / depth sums: a6 .. a9 of row r2 hold component k ^ r2 (g_pix above), so two cross-register
 				// quad exchanges and one more leave component r2, summed over the four rows, in row r2 -- 3 DPP adds for four
 				// sums, and no select: it is the sum this row owns (slot 4 + r2)
 				const float k1 = a6 + GSR_DPP_OF(a7, 0xB1), k2 = a8 + GSR_DPP_OF(a9, 0xB1);
 				// lane r2 takes sums r2, 4 + r2 and (r2 < 2) 8 + r2 to the instance's slot of the wave's plane (pending):
 				// slots 0..3 = a0..a3, 4..7 = colour r, g, b and depth, 8 = a4, 9 = a5
-				const bool lo1 = (r2 & 1) != 0;
-				pn0 = r2_hi ? (lo1 ? a3 : a2) : (lo1 ? a1 : a0);
+				pn0 = (r2_hi ? b23 : b01) + GSR_DPP_OF(r2_hi ? b01 : b23, 0x4E);
 				pn1 = k1 + GSR_DPP_OF(k2, 0x4E);
-				pn2 = lo1 ? a5 : a4;
+				pn2 = b45 + GSR_DPP_OF(b45, 0x4E);
 				pn_act = act;
-				pn_dst = plane + j * GSR_PLANE_STRIDE + r2;
+				pn_dst = plane + (e >> 4) * GSR_PLANE_STRIDE + r2;
 			}
-			__builtin_amdgcn_wave_barrier();
+		};
+		// four list entries per read (ds_read_b64), fetched one group ahead of their use; the scheduling barrier keeps the read up
+		// there (left alone, the scheduler sinks it to its use and exposes a full LDS latency per group).  Two loops, chosen once per
+		// round by the wave-uniform any_bg (as composite_fwd chooses its median phase, DESIGN s4.3): the body is written once and
+		// expanded twice
+		uint2 pk = *reinterpret_cast<const uint2*>(my_list);
+#define GSR_BWQ_WALK(BG)                                                                                                    \
+		for (int i = 0; i < n; i += GSR_BWQ_U) {                                                                            \
+			const uint2 cur = pk;                                                                                           \
+			pk = *reinterpret_cast<const uint2*>(my_list + i + GSR_BWQ_U);                                                  \
+			__builtin_amdgcn_sched_barrier(0);                                                                              \
+			turn_read(0); step(fetch(cur.x & 0xffffu), cur.x & 0xffffu, 0, BG); turn_write(0);                              \
+			turn_read(1); step(fetch(cur.x >> 16), cur.x >> 16, 1, BG); turn_write(1);                                      \
+			turn_read(2); step(fetch(cur.y & 0xffffu), cur.y & 0xffffu, 2, BG); turn_write(2);                              \
+			turn_read(3); step(fetch(cur.y >> 16), cur.y >> 16, 3, BG); turn_write(3);                                      \
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                          \
+			__builtin_amdgcn_wave_barrier();                                                                                \
+			phase2(cur, i);                                                                                                 \
+			__builtin_amdgcn_wave_barrier();                                                                                \
 		}
+		// (requesting the record of step k + 1 before evaluating step k -- two alternating register sets, what bought
+		// 7 % in the per-wave kernel -- changes nothing here: measured 0.528 against 0.527 ms)
+		if (any_bg) {
+			GSR_BWQ_WALK(GsBool<true>{})
+		} else {
+			GSR_BWQ_WALK(GsBool<false>{})
+		}
+#undef GSR_BWQ_WALK
+		thr16 -= GSR_BWQ_BATCH * 16;   // the next round's
 #pragma unroll
 		for (int qq = 0; qq < 4; qq++) {   // the last group's sums
 			turn_read(qq);

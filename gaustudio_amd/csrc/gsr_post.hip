@@ -178,6 +178,10 @@ int setup(const float* intrinsics, const float* world_to_camera, PostCam& c)
 //      weights exp(-r^2 / (2 sigma_space^2)) * exp(-dv^2 / (2 sigma_color^2))) of the depth NORMALISED to [0, 1] over the
 //      valid region with everything outside it set to 0 -- the reference filters exactly that image, zeros included --
 //      de-normalised, invalid pixels restored to their input depth.
+// A NaN depth inside new_mask is outside the valid region, as in the reference (nanmin / nanmax, :205-232): skipped by the
+// min / max, 0 in the normalised image, returned as it came; new_mask itself does not depend on the depth.
+// d = 0 (radius lrint(1.5 sigma_space)): the erosion window is 2 radius + 1 -- this library's choice, the reference only ever
+// passes d = 3.
 // OpenCV evaluates the colour weight through a 4096-bin interpolated table; here it is expf directly (|dw| < 1e-7).
 __device__ __forceinline__ uint32_t f2ord(float f)
 {
@@ -201,7 +205,8 @@ __global__ __launch_bounds__(256) void bilateral_mask_minmax_kernel(const float*
 				if (xx >= 0 && xx < W && yy >= 0 && yy < H && mask[(size_t)yy * W + xx] == 0) ok = false;
 			}
 		new_mask[(size_t)y * W + x] = ok ? 1 : 0;
-		if (ok) lo = hi = f2ord(depth[(size_t)y * W + x]);
+		const float dp = depth[(size_t)y * W + x];
+		if (ok && dp == dp) lo = hi = f2ord(dp);   // nanmin / nanmax: a NaN depth is outside the valid region
 	}
 #pragma unroll
 	for (int o = 32; o > 0; o >>= 1) {
@@ -214,6 +219,17 @@ __global__ __launch_bounds__(256) void bilateral_mask_minmax_kernel(const float*
 	}
 }
 
+// cv2's BORDER_REFLECT_101 (borderInterpolate): reflect about the first / last sample until the index is inside -- an image
+// narrower than the radius is crossed more than once -- i.e. |p| mod 2(n - 1), folded; a single row / column gives 0.
+__device__ __forceinline__ int reflect101(int p, int n)
+{
+	if ((unsigned)p < (unsigned)n) return p;
+	if (n == 1) return 0;
+	const int m = 2 * (n - 1);
+	p = (p < 0 ? -p : p) % m;
+	return p < n ? p : m - p;
+}
+
 __global__ __launch_bounds__(256) void bilateral_filter_kernel(const float* __restrict__ depth, const uint8_t* __restrict__ new_mask,
                                                                int W, int H, int radius, float space_coeff, float color_coeff,
                                                                const uint32_t* __restrict__ mm, float* __restrict__ out)
@@ -222,15 +238,14 @@ __global__ __launch_bounds__(256) void bilateral_filter_kernel(const float* __re
 	if (x >= W || y >= H) return;
 	const size_t p = (size_t)y * W + x;
 	const float d0 = depth[p];
-	if (mm[1] == 0u || !new_mask[p]) { out[p] = d0; return; }   // no valid pixel at all / invalid pixel: unchanged
+	// no valid pixel at all / invalid pixel / NaN depth (outside the reference's valid region, restored afterwards): unchanged
+	if (mm[1] == 0u || !new_mask[p] || d0 != d0) { out[p] = d0; return; }
 	const float vmin = ord2f(mm[0]), vmax = ord2f(mm[1]);
 	const float range = vmax - vmin;
 	auto norm_at = [&](int xx, int yy) -> float {   // the image cv2.bilateralFilter is handed, BORDER_REFLECT_101
-		xx = xx < 0 ? -xx : (xx >= W ? 2 * W - 2 - xx : xx);
-		yy = yy < 0 ? -yy : (yy >= H ? 2 * H - 2 - yy : yy);
-		xx = min(max(xx, 0), W - 1); yy = min(max(yy, 0), H - 1);   // (images narrower than the radius)
-		const size_t q = (size_t)yy * W + xx;
-		return new_mask[q] ? (depth[q] - vmin) / range : 0.f;
+		const size_t q = (size_t)reflect101(yy, H) * W + reflect101(xx, W);
+		const float dq = depth[q];
+		return (new_mask[q] && dq == dq) ? (dq - vmin) / range : 0.f;   // a NaN depth is 0 in that image, like an invalid pixel
 	};
 	const float v0 = (d0 - vmin) / range;
 	// cv2: a constant image is copied through (|max - min| < FLT_EPSILON of the NORMALISED image: never for range > 0,

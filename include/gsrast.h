@@ -411,7 +411,14 @@ int gsr_depth_epilogue(const float* depth, const float* opacity, float min_opaci
  * u8 (valid iff the whole d x d window is valid), filtered[H,W]: the bilateral filter (OpenCV's float32 definition:
  * radius max(d/2,1), circular window, reflect-101 border) of the depth normalised over new_mask with everything else
  * set to 0, de-normalised; pixels outside new_mask keep their input depth.  d odd (or 0 = from sigma_space);
- * scratch2 = 8 bytes of device memory.  Parity with cv2 is unpinned (the library is not in this image): restated
+ * scratch2 = 8 bytes of device memory.
+ * Border: cv2's BORDER_REFLECT_101, reflected until the index is inside (|p| mod 2(n - 1), folded; a single row or column
+ * gives index 0), so an image narrower than the radius is crossed more than once.
+ * NaN: a NaN depth inside new_mask is outside the valid region, as with the reference's nanmin / nanmax: it does not enter
+ * the min / max, is 0 in the normalised image and comes back as NaN; new_mask does not depend on the depth values.
+ * d = 0: radius = lrint(1.5 sigma_space) (at least 1) and the erosion window is 2 radius + 1.  That window is this
+ * library's own choice: the reference only ever passes d = 3 (cv2.dilate with a 0 x 0 kernel has no meaning to follow).
+ * sigma <= 0 counts as 1.  Parity with cv2 is unpinned (the library is not in this image): restated
  * from its published algorithm, colour weight by expf instead of cv2's 4096-bin interpolated table. */
 int gsr_masked_bilateral(const float* depth, const unsigned char* mask, int width, int height, int d, float sigma_color,
                          float sigma_space, float* filtered, unsigned char* new_mask, unsigned int* scratch2, void* stream);

@@ -1,7 +1,13 @@
 """Post-render epilogue: depth -> points / normals.
 CPU: the numpy restatement (oracle/post_oracle.py) against outputs of the reference's own Camera class
 (tests/golden/py_post.npz).  GPU: the HIP kernels (through the C ABI) against the same fixture and, at 1080p,
-against the restatement."""
+against the restatement.
+
+The float32 model that defines these kernels operation by operation is tests/post_model.py: tests/test_post_model.py pins it
+(CPU) to the same fixture and to the restatement, tests/test_gpu_post_edges.py compares the kernels with it bit for bit
+(points, normals, epilogue) and under a derived bound (bilateral filter) on edge inputs -- image sizes around the blocks,
+cameras with a general last intrinsic row or a non-rigid extrinsic, depths on the validity bounds, non-finite depths,
+images narrower than the filter radius."""
 import os
 
 import numpy as np

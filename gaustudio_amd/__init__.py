@@ -15,5 +15,7 @@ from .pcd_init import depth_seeds, mean_dist2, pcd_init_from_ply, point_seeds, s
 # Scaffold-GS: anchors + MLPs + camera -> Gaussians -> render (the anchor-based family of the reference)
 from .scaffold import (ScaffoldGaussians, ScaffoldModel, decode, decode_torch, render_scaffold,  # noqa: F401,E402
                        visible_anchors)
+# the training loss: (1 - lambda) L1 + lambda (1 - SSIM), fused forward and backward
+from .losses import l1_loss, photometric_loss, photometric_loss_with_parts, ssim, ssim_map  # noqa: F401,E402
 
 __version__ = "0.1.0"

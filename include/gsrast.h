@@ -956,6 +956,23 @@ int gsr_scaffold_backward(gsr_alloc_fn workspace_alloc, void* workspace_ctx, con
                           float* d_anchor, float* d_anchor_feat, float* d_offset, float* d_scaling, float* const d_weights[16],
                           void* stream);
 
+/* ---- The photometric loss of 3DGS training (csrc/gsr_loss.hip): loss = (1 - lambda) L1 + lambda (1 - SSIM), SSIM with the
+ * 11 x 11 Gaussian window (sigma 1.5) under zero padding.  Additive to ABI 6.  Contract, float order included: INTEGRATION.md
+ * s24 (its definition to the bit: tests/loss_model.py); design: DESIGN.md s21.  image / target: device, f32, contiguous,
+ * [planes, height, width].  planes, height, width >= 1 and planes * height * width < 2^31, 0 <= lambda_dssim <= 1
+ * (GSR_ERR_ARG otherwise).  No atomics: bit-identical from run to run and on any stream.  No wait. ---- */
+
+/* out3 (device) = {loss, l1, ssim} as f32, formed in f64 from per-workgroup f64 partials (scratch from the allocator callback,
+ * once).  ssim_map [planes,H,W] (may be NULL) receives the per-pixel SSIM; maps [3,planes,H,W] (may be NULL: forward only)
+ * receives what gsr_photometric_bwd convolves. */
+int gsr_photometric_fwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* image, const float* target,
+                        long long planes, int height, int width, float lambda_dssim, float* ssim_map, float* maps, float* out3,
+                        void* stream);
+/* grad_image [planes,H,W] = *grad_loss * d loss / d image, from the maps of a forward on the same image and target.
+ * grad_loss: one f32 in DEVICE memory, the upstream gradient of the scalar loss. */
+int gsr_photometric_bwd(const float* image, const float* target, const float* maps, long long planes, int height, int width,
+                        float lambda_dssim, const float* grad_loss, float* grad_image, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

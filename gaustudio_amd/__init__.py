@@ -17,5 +17,7 @@ from .scaffold import (ScaffoldGaussians, ScaffoldModel, decode, decode_torch, r
                        visible_anchors)
 # the training loss: (1 - lambda) L1 + lambda (1 - SSIM), fused forward and backward
 from .losses import l1_loss, photometric_loss, photometric_loss_with_parts, ssim, ssim_map  # noqa: F401,E402
+# the optimiser half of training: a one-launch (visibility-sparse) Adam and adaptive density control
+from .optim import DensifyReport, DensityControl, GaussianAdam  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -983,6 +983,66 @@ void gsr_set_profiling(int enable);
 int gsr_last_forward_ms(float ms[5]);
 int gsr_last_backward_ms(float ms[2]);
 
+/* ---- The optimiser step and adaptive density control of 3DGS training (csrc/gsr_optim.hip).  Additive to ABI 6.  Contract,
+ * float order included: INTEGRATION.md s25 (its definition to the bit: tests/optim_model.py); design: DESIGN.md s22.
+ * Every tensor: device, 4-byte elements, contiguous, [num_rows, width].  0 <= num_rows and num_rows * 45 < 2^31, widths
+ * within [0, 45] (GSR_ERR_ARG otherwise).  No atomics: bit-identical from run to run and on any stream. ---- */
+
+/* One parameter group of gsr_adam_step (HOST).  grad NULL or width 0: the group is skipped. */
+typedef struct gsr_adam_group {
+	float* param;
+	const float* grad;
+	float* exp_avg;
+	float* exp_avg_sq;
+	double lr;
+	int width;
+	int reserved;
+} gsr_adam_group;
+
+/* One launch for all groups: torch.optim.Adam without weight decay or amsgrad at step `step` >= 1 (the caller counts).  The
+ * per-group constants 1 - beta1, 1 - beta2, sqrt(1 - beta2^step) and lr / (1 - beta1^step) are formed here in f64, rounded to
+ * f32 once and passed to the kernel by value; nothing reads the device.  visible (device, int32 [num_rows], may be NULL): rows
+ * with visible <= 0 keep parameter and both moments.  1 <= num_groups <= 6.  No wait. */
+int gsr_adam_step(const gsr_adam_group* groups, int num_groups, int num_rows, double beta1, double beta2, double eps,
+                  long long step, const int* visible, void* stream);
+
+/* Rows with radii > 0: grad_accum += sqrt(gx gx + gy gy) of means2d_grad [num_rows,3], denom += 1, max_radii = max(max_radii,
+ * radii).  No wait. */
+int gsr_density_accumulate(int num_rows, const float* means2d_grad, const int* radii, float* grad_accum, int* denom,
+                           int* max_radii, void* stream);
+
+/* The classify and scan half of a compaction.  pos (device, int32 [3 num_rows + 1]) receives the exclusive scan of the three
+ * per-row flags {the source survives, its clone is emitted, its children are emitted}, laid out flag-major, so that pos[i],
+ * pos[num_rows + i] and pos[2 num_rows + i] + c * (pos[3 num_rows] - pos[2 num_rows]) are the output rows of source i, of its
+ * clone and of its child c.  prune_mask (device, u8 [num_rows]) non-NULL: a plain prune -- a source survives where the mask is
+ * 0 and nothing else is read.  Otherwise the densification of INTEGRATION.md s25 with thresholds formed here in f64;
+ * max_screen_size < 0: no screen- and world-size tests.  totals_host[4] (HOST) = {survivors, clones, split sources with
+ * children, rows after}.  Waits on `stream` once, for the totals; GSR_ERR_ARG, nothing else written, when rows after * 45
+ * >= 2^31.  Scratch from the allocator callback, once. */
+int gsr_densify_classify(gsr_alloc_fn workspace_alloc, void* workspace_ctx, int num_rows, const float* scaling,
+                         const float* opacity, const float* grad_accum, const int* denom, const int* max_radii,
+                         const unsigned char* prune_mask, float max_grad, double percent_dense, double extent,
+                         double min_opacity, int max_screen_size, int n_split, int* pos, long long* totals_host, void* stream);
+
+#define GSR_COMPACT_COPY 0     /* the value goes to every output row of its source; moments: carried by the survivor, else 0 */
+#define GSR_COMPACT_XYZ 1      /* as COPY, a child gets xyz + R(q / |q|) (exp(scaling) * noise) */
+#define GSR_COMPACT_SCALING 2  /* as COPY, a child gets scaling - log(0.8 n_split) */
+#define GSR_COMPACT_STATS 3    /* three per-row statistics, carried by survivors only (their other rows are not written) */
+
+/* One group of gsr_densify_emit (HOST): a parameter with its two moments (or three statistics), source and destination. */
+typedef struct gsr_compact_group {
+	const void* src[3];
+	void* dst[3];
+	int width;
+	int kind;
+} gsr_compact_group;
+
+/* The emit half: one launch writes every destination row of every group from `pos`.  noise: f32 [num_rows, n_split, 3] by
+ * SOURCE row, read for rows with children only (may be NULL when pos holds none).  scaling / rotation: the source tensors the
+ * children's positions are formed from.  Sources are never written.  1 <= num_groups <= 8.  No wait. */
+int gsr_densify_emit(int num_rows, int n_split, const gsr_compact_group* groups, int num_groups, const int* pos,
+                     const float* noise, const float* scaling, const float* rotation, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

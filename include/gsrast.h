@@ -973,6 +973,27 @@ int gsr_photometric_fwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const
 int gsr_photometric_bwd(const float* image, const float* target, const float* maps, long long planes, int height, int width,
                         float lambda_dssim, const float* grad_loss, float* grad_image, void* stream);
 
+/* ---- The geometric regularisers of 2D Gaussian surfel training (csrc/gsr_geoloss.hip): loss = lambda_normal mean(1 - <N, n a1>)
+ * + lambda_dist mean(a6) on the surfel operator's allmap [7,height,width] (device, f32, contiguous), n the normal of the
+ * blended depth (1 - depth_ratio) nan_to_num(a0 / a1) + depth_ratio nan_to_num(a5) by central differences of the camera-space
+ * points, 0 on the one-pixel border.  Additive to ABI 6.  Contract, float order included: INTEGRATION.md s26 (its definition
+ * to the bit: tests/geoloss_model.py); design: DESIGN.md s23.  height, width >= 1 and 7 * height * width < 2^31,
+ * 0 <= depth_ratio <= 1, lambdas finite and >= 0, fx, fy, cx, cy finite, fx and fy non-zero (GSR_ERR_ARG otherwise).  No atomics:
+ * bit-identical from run to run and on any stream.  No wait. ---- */
+
+/* out3 (device) = {loss, normal_loss, dist_loss} as f32, formed in f64 from per-workgroup f64 partials (scratch from the allocator
+ * callback, once).  maps [10,H,W] (may be NULL) receives {expected depth, median depth, blended depth, n a1 (3 planes), the
+ * rendered normal (3 planes), 1 - <N, n a1>}; viewmatrix (device, 16 floats as the operator takes it, may be NULL) turns the two
+ * normals of `maps` to world space, v -> sum_i v_i viewmatrix[4 j + i].  The loss does not depend on it. */
+int gsr_surfel_geoloss_fwd(gsr_alloc_fn workspace_alloc, void* workspace_ctx, const float* allmap, int height, int width, float fx,
+                           float fy, float cx, float cy, float depth_ratio, float lambda_normal, float lambda_dist,
+                           const float* viewmatrix, float* maps, float* out3, void* stream);
+/* grad_allmap [7,H,W] = *grad_loss * d loss / d allmap, every plane written; nothing is taken from a forward.  a1 is a constant
+ * in the factor n a1; a pixel whose a0 / a1 is not finite gets 0 in planes 0 and 1, one whose a5 is not finite 0 in plane 5.
+ * grad_loss: one f32 in DEVICE memory, the upstream gradient of the scalar loss. */
+int gsr_surfel_geoloss_bwd(const float* allmap, int height, int width, float fx, float fy, float cx, float cy, float depth_ratio,
+                           float lambda_normal, float lambda_dist, const float* grad_loss, float* grad_allmap, void* stream);
+
 /* Per-stage GPU time, averaged over every gsr_forward / gsr_backward call made in this process (any thread) since
  * gsr_set_profiling(1): milliseconds for {preprocess, scan (tile histogram + scans + row offsets), scatter, sort, composite} (forward)
  * or {composite_bwd, preprocess_bwd} (backward), measured with HIP events recorded on the launch stream.

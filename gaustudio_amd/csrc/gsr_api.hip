@@ -145,7 +145,7 @@ int env_int(const char* name, int dflt)
 }
 std::atomic<int> g_opt_tight{env_int("GSR_TIGHT_BINNING", 1)};     // bin into gs_tight_rect (0: the reference's squares)
 std::atomic<int> g_opt_cull{env_int("GSR_CULL", 1)};               // composite_fwd wave culling + pcut pre-test
-std::atomic<int> g_opt_fwd_variant{env_int("GSR_FWD_VARIANT", 0)}; // 0: per-quarter (4x4) instance lists, 1: per-wave (8x8)
+std::atomic<int> g_opt_fwd_variant{env_int("GSR_FWD_VARIANT", 0)}; // 0: per-quarter (4x4) instance lists; 1 is refused
 std::atomic<int> g_opt_bwd_variant{env_int("GSR_BWD_VARIANT", -1)};   // -1: from gsr_selftest; bit 0: select on T
 std::atomic<int> g_opt_speculative{env_int("GSR_SPECULATIVE", 1)}; // launch binning + compositing before R is known
 std::atomic<int> g_opt_tile_order{env_int("GSR_TILE_ORDER", 1)};   // backward of a skewed frame: tiles longest walk first (0: always XCD-banded)
@@ -545,19 +545,9 @@ static int forward_impl(const gsr_options* opt, gsr_alloc_fn geometry_alloc, voi
 		const int rc = check_sticky("gsr_forward");
 		if (rc < 0) return rc;
 	}
-	Resolved ro = resolve_options(opt);
-#ifndef GSR_AB_VARIANTS
+	const Resolved ro = resolve_options(opt);
 	if (ro.fwd_variant == 1)
-		return fail(GSR_ERR_ARG, "gsr_forward: fwd_variant 1 (the per-wave A/B kernel) is not in this build (make AB=1; gsr_get_option(\"ab_variants\"))", __FILE__, __LINE__);
-#endif
-	if (ro.fast_exp && ro.fwd_variant == 1) {
-		// the per-wave A/B kernel has no v_exp_f32 form.  Asked for both: an error.  fast_exp merely inherited from the
-		// process default (on since round 4): the A/B switch wins and the call runs in the reproducible mode;
-		// the backward follows the forward's recorded mode the same way
-		if (ro.fast_exp_explicit)
-			return fail(GSR_ERR_ARG, "gsr_forward: fast_exp needs the per-quarter compositing kernels (fwd_variant 0)", __FILE__, __LINE__);
-		ro.fast_exp = 0;
-	}
+		return fail(GSR_ERR_ARG, "gsr_forward: fwd_variant 1 (the per-wave compositing kernel) is not in this build", __FILE__, __LINE__);
 	const GeomLayout gl((size_t)P);
 	const ImgLayout il(width, height);
 	if (il.gx > 65535 || il.gy > 65535) return fail(GSR_ERR_ARG, "gsr_forward: image too large", __FILE__, __LINE__);
@@ -591,8 +581,7 @@ static int forward_impl(const gsr_options* opt, gsr_alloc_fn geometry_alloc, voi
 		const int n[4] = {16, 16, 3, 3};
 		const bool banded = ro.band_hi > 0 || ro.band_lo > 0;
 		const uint32_t word = (ro.fast_exp ? GSR_CTL_OPT_FAST_EXP : 0u) | (ro.tight ? GSR_CTL_OPT_TIGHT : 0u) |
-		                      (ro.cull ? GSR_CTL_OPT_CULL : 0u) | (ro.fwd_variant == 1 ? GSR_CTL_OPT_WAVE_LISTS : 0u) |
-		                      (banded ? GSR_CTL_OPT_BAND : 0u) | (ro.forward_only ? GSR_CTL_OPT_FORWARD_ONLY : 0u);
+		                      (ro.cull ? GSR_CTL_OPT_CULL : 0u) | (banded ? GSR_CTL_OPT_BAND : 0u) | (ro.forward_only ? GSR_CTL_OPT_FORWARD_ONLY : 0u);
 		HIP_TRY(stage_small(src, dst, n, s, &ctl->opts, word, reinterpret_cast<uint32_t*>(ctl), 8));
 	}
 
@@ -642,7 +631,6 @@ static int forward_impl(const gsr_options* opt, gsr_alloc_fn geometry_alloc, voi
 
 	DevState& ds = dev_state();
 	const bool nocull = ro.cull == 0;
-	const bool wave_lists = ro.fwd_variant == 1;
 	bool skew_now = g_opt_tile_order.load() != 0 && ds.skew.load() != 0;
 	auto launch_rest = [&](uint32_t cap, int long_level) -> int {
 		const bool with_long = long_level > 0;
@@ -680,7 +668,7 @@ static int forward_impl(const gsr_options* opt, gsr_alloc_fn geometry_alloc, voi
 		}
 		launch_composite_fwd(il, width, height, ranges, point_list, recs, out_color, out_depth, out_median_depth,
 		                     out_opacity, final_T, n_contrib, med_pos, ctl, cap,
-		                     long_level >= 2 ? 0xffffffffu : (long_level == 1 ? GSR_SORT_GIANT : GSR_SORT_LDS_MAX), nocull, wave_lists, ro.fast_exp != 0, order,
+		                     long_level >= 2 ? 0xffffffffu : (long_level == 1 ? GSR_SORT_GIANT : GSR_SORT_LDS_MAX), nocull, ro.fast_exp != 0, order,
 		                     tile_count /* dead after binning: instances staged per tile, gsr_inspect_staged */, s);
 		STAGE_CHECK("composite_fwd", debug, s);
 		tm.mark();
@@ -787,10 +775,10 @@ size_t gsr_backward_scratch_bytes(int P, int R)
 	return BwdLayout((size_t)(P > 0 ? P : 0), (size_t)(R > 0 ? R : 0)).total;
 }
 
-// composite_bwd variant: bit 0 = keep a select on T (devices where v_rcp_f32(1.0) != 1.0)
-static int bwd_variant(int opt, hipStream_t s)
+// composite_bwd: keep a select on T?  (bit 0 of the option, or -- auto -- a device where v_rcp_f32(1.0) != 1.0)
+static bool bwd_variant(int opt, hipStream_t s)
 {
-	if (opt >= 0) return opt;
+	if (opt >= 0) return (opt & 1) != 0;
 	DevState& ds = dev_state();
 	int st = ds.selftest.load();
 	if (st < 0) {
@@ -798,7 +786,7 @@ static int bwd_variant(int opt, hipStream_t s)
 		if (st < 0) st = 0;
 		ds.selftest.store(st);
 	}
-	return (st & 3) == 3 ? 0 : 1;
+	return (st & 3) != 3;
 }
 
 static int backward_impl(const gsr_options* opt, int parts, int sh_g0, int sh_g1, int P, int D, int M, int R, const float* background, int width, int height,
@@ -929,8 +917,7 @@ static int backward_impl(const gsr_options* opt, int parts, int sh_g0, int sh_g1
 		Resolved ro = resolve_options(opt);
 		{
 			const int fwd_mode = fwd.fast_exp;
-			// fast_exp not named by the caller: the mode the forward of these buffers ran in (which may itself have left the
-			// process default for an A/B variant without a v_exp_f32 kernel, see forward_impl) -- from the host-side map or, for
+			// fast_exp not named by the caller: the mode the forward of these buffers ran in -- from the host-side map or, for
 			// buffers it does not know, from the forward's own control word (lookup_forward): never the process default
 			if (!ro.fast_exp_explicit) ro.fast_exp = fwd_mode;
 			if (fwd_mode != (ro.fast_exp != 0))
@@ -945,15 +932,9 @@ static int backward_impl(const gsr_options* opt, int parts, int sh_g0, int sh_g1
 			if (((c.opts & GSR_CTL_OPT_FAST_EXP) != 0u) != (ro.fast_exp != 0))
 				return fail(GSR_ERR_ARG, "gsr_backward: fast_exp differs from the forward that produced these buffers", __FILE__, __LINE__);
 		}
-		int variant = bwd_variant(ro.bwd_variant, s);
-#ifndef GSR_AB_VARIANTS
-		if (variant & 2)
-			return fail(GSR_ERR_ARG, "gsr_backward: bwd_variant bit 1 (the per-wave A/B kernel) is not in this build (make AB=1; gsr_get_option(\"ab_variants\"))", __FILE__, __LINE__);
-#endif
-		if (ro.fast_exp) {
-			if (variant & 2) return fail(GSR_ERR_ARG, "gsr_backward: fast_exp needs the per-quarter kernel (bwd_variant bit 1 clear)", __FILE__, __LINE__);
-			variant |= 8;   // bit 3: the forward used the hardware exp -- the backward takes the same decisions with it
-		}
+		if (ro.bwd_variant >= 0 && (ro.bwd_variant & 2))
+			return fail(GSR_ERR_ARG, "gsr_backward: bwd_variant bit 1 (the per-wave compositing kernel) is not in this build", __FILE__, __LINE__);
+		const bool tsel = bwd_variant(ro.bwd_variant, s);
 		if (fwd.skew) {
 			uint32_t* tw = reinterpret_cast<uint32_t*>(const_cast<char*>(image_buffer) + il.tile_work);
 			uint32_t* to = reinterpret_cast<uint32_t*>(const_cast<char*>(image_buffer) + il.tile_order);
@@ -962,7 +943,8 @@ static int backward_impl(const gsr_options* opt, int parts, int sh_g0, int sh_g1
 		}
 		launch_composite_bwd(il, width, height, bgv, ranges, point_list, recs, goff, final_T, n_contrib, med_pos, dL_dpix,
 		                     dL_dpix_depth, dL_dpix_median_depth, dL_dpix_final_opacity, rows, row_flags,
-		                     reinterpret_cast<const GsCtl*>(image_buffer + il.ctl), variant, s);
+		                     reinterpret_cast<const GsCtl*>(image_buffer + il.ctl), tsel,
+		                     ro.fast_exp != 0 /* the forward's mode: the backward takes the same decisions with the same exp */, s);
 		STAGE_CHECK("composite_bwd", debug, s);
 	}
 	tm.mark();
@@ -1120,13 +1102,6 @@ int gsr_get_option(const char* name)
 	if (n == "tile_row_lo") return g_opt_band_lo.load();
 	if (n == "tile_row_hi") return g_opt_band_hi.load();
 	if (n == "bin_capacity") return (int)dev_state().cap.load();
-	if (n == "ab_variants") {   // read-only: were the superseded per-wave compositing kernels (fwd_variant 1, bwd_variant bit 1) compiled in?
-#ifdef GSR_AB_VARIANTS
-		return 1;
-#else
-		return 0;
-#endif
-	}
 	return -1;
 }
 

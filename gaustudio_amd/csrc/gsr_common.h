@@ -55,8 +55,7 @@ struct GsCtl {
 #define GSR_CTL_OPT_FAST_EXP 1u     // compositing used gs_exp_hw: the backward must take its decisions with it as well
 #define GSR_CTL_OPT_TIGHT 2u
 #define GSR_CTL_OPT_CULL 4u
-#define GSR_CTL_OPT_WAVE_LISTS 8u
-#define GSR_CTL_OPT_BAND 16u
+#define GSR_CTL_OPT_BAND 16u            // (8u is not used)
 #define GSR_CTL_OPT_FORWARD_ONLY 32u   // the forward kept nothing for a backward (gsr_options.forward_only)
 
 // Per-instance block masks of the forward (bit 4*row + col: which 4x4 pixel blocks of the tile the instance can touch,
@@ -385,7 +384,9 @@ __device__ __forceinline__ void cov2d_common(const float3 mean, float fx, float 
 // ---------------------------------------------------------------------------------------------
 // Pixel <-> slot mapping of the tile-major per-pixel state (final_T, n_contrib): slot s of a 16x16 tile is
 // pixel (lx, ly) of 8x8 quadrant q = s>>6 = (ly>>3)*2 + (lx>>3), lane l = s&63 = (ly&7)*8 + (lx&7).
-// composite_fwd and composite_bwd both run 4 wave64 per tile, wave q on quadrant q (slot = thread id).
+// composite_fwd and composite_bwd both run 4 wave64 per tile, wave q on quadrant q; inside the wave they give every 16-lane
+// quarter a 4x4 block and compute the slot from that.  Where slot = thread id (the surfel kernels, inspect_image_kernel):
+// gs_pixel_of_thread.
 // (A 2-pixel-per-lane forward was measured in round 1: 0.55 ms vs 0.46 ms at C3 -- the larger culling box costs
 // more than packed arithmetic saves; round 2 moved the backward to this layout as well, docs/DESIGN_history_r1-r4.md s4.3.)
 // ---------------------------------------------------------------------------------------------
@@ -396,45 +397,13 @@ __device__ __forceinline__ void gs_pixel_of_thread(int tid, int& lx, int& ly)
 	ly = ((w >> 1) << 3) + (l >> 3);
 }
 
-// Conservative wave-level cull.  Returns false only if NO pixel centre (x,y) in the closed box
-// [bx0,bx1] x [by0,by1] can pass the per-pixel test `0 >= power >= pcut`, where
-//   power(d) = ha*dx^2 + nb*dx*dy + hc*dy^2,  d = centre - pixel   (ha,nb,hc,pcut from the record).
-// For a negative-definite form the maximum over the box lies on the edges nearest to the centre
-// (power decreases along every ray from the centre); it is found in closed form per near edge.
-// A slack of 0.05 + 1e-5*|terms| in `power` covers every rounding difference to the per-pixel
-// evaluation, so culling a (wave, Gaussian) pair is exactly equivalent to evaluating its 64 pixels
-// and rejecting each: results stay bit-identical, only work is removed.
-__device__ __forceinline__ bool gs_box_may_touch(const float4 A, const float4 B, float bx0, float by0, float bx1,
-                                                 float by1)
-{
-	const float ha = A.z, nb = A.w, hc = B.x, pcut = B.w;
-	if (!(pcut <= 0.f)) return false;            // opacity < 1/255: no pixel can reach alpha >= 1/255
-	const float X0 = A.x - bx1, X1 = A.x - bx0;  // range of dx over the box
-	const float Y0 = A.y - by1, Y1 = A.y - by0;
-	const float xn = fminf(fmaxf(0.f, X0), X1);  // point of the range nearest to 0
-	const float yn = fminf(fmaxf(0.f, Y0), Y1);
-	if (xn == 0.f && yn == 0.f) return true;     // centre inside the box
-	if (!(ha < 0.f && hc < 0.f && 4.f * ha * hc - nb * nb > 0.f)) return true;   // not negative definite: keep
-	float best = -3.0e38f;
-	float mag = 0.f;
-	if (xn != 0.f) {
-		const float dy = fminf(fmaxf(-0.5f * nb * xn * __builtin_amdgcn_rcpf(hc), Y0), Y1);
-		const float t0 = ha * xn * xn, t1 = (hc * dy + nb * xn) * dy;
-		best = t0 + t1;
-		mag = fabsf(t0) + fabsf(hc * dy * dy) + fabsf(nb * xn * dy);
-	}
-	if (yn != 0.f) {
-		const float dx = fminf(fmaxf(-0.5f * nb * yn * __builtin_amdgcn_rcpf(ha), X0), X1);
-		const float t0 = hc * yn * yn, t1 = (ha * dx + nb * yn) * dx;
-		best = fmaxf(best, t0 + t1);
-		mag = fmaxf(mag, fabsf(t0) + fabsf(ha * dx * dx) + fabsf(nb * yn * dx));
-	}
-	return best >= pcut - (0.05f + 1e-5f * mag);
-}
-
-// Which of the NB x NB 4x4-pixel blocks (bit NB*row + col) of the square of pixels starting at (tx0, ty0) can hold a
-// pixel with 0 >= power >= pcut?  (NB = 4: the 16x16 tile, composite_fwd; NB = 2: a wave's 8x8 block, composite_bwd.)  Conservative
-// like gs_box_may_touch, organised by rows of blocks: for the band of dy a block row spans, the dx-extent
+// Conservative block cull.  Which of the NB x NB 4x4-pixel blocks (bit NB*row + col) of the square of pixels starting at
+// (tx0, ty0) can hold a pixel centre that passes the per-pixel test `0 >= power >= pcut`, where
+//   power(d) = ha*dx^2 + nb*dx*dy + hc*dy^2,  d = centre - pixel   (ha,nb,hc,pcut from the record)?
+// (NB = 4: the 16x16 tile, composite_fwd; NB = 2: a wave's 8x8 block, composite_bwd.)  A bit is cleared only if NO pixel of
+// the block can pass: the slack below covers every rounding difference to the per-pixel evaluation, so culling a
+// (block, Gaussian) pair is exactly equivalent to evaluating its 16 pixels and rejecting each -- results stay bit-identical,
+// only work is removed.  Organised by rows of blocks: for the band of dy a block row spans, the dx-extent
 // [lo, hi] of the region {power >= pc} is found in closed form (the roots of the quadratic in dx at the band's two
 // ends, plus the region's extreme points in x when they lie in the band -- the extent is a concave/convex function of
 // dy, so those three candidates contain its extremum); a block is hit iff its dx range meets [lo, hi].  pc = pcut minus

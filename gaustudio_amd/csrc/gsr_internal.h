@@ -132,7 +132,7 @@ void launch_tile_sort(int T, bool with_short, int long_level, const uint2* range
                       uint32_t* point_list, char* queue, size_t R, GsCtl* ctl, uint32_t cap, uint32_t* host_err, hipStream_t s);
 void launch_composite_fwd(const ImgLayout& il, int W, int H, const uint2* ranges, const uint32_t* point_list,
                           const GsRec* recs, float* out_color, float* out_depth, float* out_median,
-                          float* out_opacity, float* final_T, uint32_t* n_contrib, uint32_t* med_pos, GsCtl* ctl, uint32_t cap, uint32_t max_sorted, bool nocull, bool wave_lists, bool fast_exp,
+                          float* out_opacity, float* final_T, uint32_t* n_contrib, uint32_t* med_pos, GsCtl* ctl, uint32_t cap, uint32_t max_sorted, bool nocull, bool fast_exp,
                           const uint32_t* tile_order, uint32_t* staged_out, hipStream_t s);
 void launch_tile_order_fwd(int T, const uint2* ranges, uint32_t* order, const GsCtl* ctl, uint32_t cap, hipStream_t s);
 
@@ -200,12 +200,12 @@ void launch_band_classes(int P, const int* radii, const GsRec* recs, int split, 
 // starts such a tile late is the kernel's tail): work[t] = the tile's longest walk (max n_contrib), tiles ordered by
 // descending work class (counting sort, 4 classes per octave).  Two small launches, only when the forward saw skew.
 void launch_tile_order(int T, const uint32_t* n_contrib, uint32_t* tile_work, uint32_t* tile_order, hipStream_t s);
-// variant: 0 = default; other values select A/B variants of the kernel (gsr_set_option("bwd_variant", v))
+// tsel: the select on T for a device that fails gsr_selftest (or gsr_set_option("bwd_variant", 1)); fast_exp: the forward's mode
 void launch_composite_bwd(const ImgLayout& il, int W, int H, const GsBg& bg, const uint2* ranges,
                           const uint32_t* point_list, const GsRec* recs, const uint32_t* goff, const float* final_T,
                           const uint32_t* n_contrib, const uint32_t* med_pos, const float* dL_dpix, const float* dL_dpix_depth,
                           const float* dL_dpix_median, const float* dL_dpix_opacity, float* rows, uint8_t* row_flags,
-                          const GsCtl* ctl, int variant, hipStream_t s);
+                          const GsCtl* ctl, bool tsel, bool fast_exp, hipStream_t s);
 // parts: GSR_PART_GEOM = the per-Gaussian geometry kernel (all P Gaussians); GSR_PART_SH = the SH kernel over
 // the Gaussians [sh_g0, sh_g1) (a multiple-of-256 start; lets a caller interleave a collective per chunk)
 #define GSR_PART_GEOM 1

@@ -27,25 +27,9 @@ __device__ __constant__ float bSH_C3[7] = {-0.5900435899266435f, 2.8906114426405
                                             0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
                                             -0.5900435899266435f};
 
-// Lane-swap folds used by phase 2 of composite_bwd (lanes that belong to the same pair sit 8, 16 and 32 lanes apart):
-//   half_swap_sum(a, b): lanes 0-31 get a[l] + a[l+32], lanes 32-63 get b[l-32] + b[l]   (1 swap + 1 add for two
-//   quantities); row_swap_sum(p, q): 16-lane rows (0,1,2,3) get p.r0+p.r1, q.r0+q.r1, p.r2+p.r3, q.r2+q.r3.
-// Doing these "transposing" steps on pairs of quantities shrinks ten per-lane quantities to three registers whose
-// rows carry different quantities; GSR_DPP_ADD(v, ctrl) is a fused v_add_f32_dpp.
-#define GSR_DPP_ADD(v, ctrl) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, true))
+// GSR_DPP_OF(v, ctrl): v of the lane that the DPP control names (0xB1: lane ^ 1, 0x4E: lane ^ 2 within a quad).  As the operand
+// of an add it becomes one v_add_f32_dpp: the folds of composite_bwd's phase 2 are written with it.
 #define GSR_DPP_OF(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, true))
-__device__ __forceinline__ float half_swap_sum(float a, float b)
-{
-	// v_permlane32_swap(X, Y): X.rows23 <-> Y.rows01
-	const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-	return __uint_as_float(t[0]) + __uint_as_float(t[1]);
-}
-__device__ __forceinline__ float row_swap_sum(float p, float q)
-{
-	// v_permlane16_swap(X, Y): X.row1 <-> Y.row0, X.row3 <-> Y.row2
-	const auto t = __builtin_amdgcn_permlane16_swap(__float_as_uint(p), __float_as_uint(q), false, false);
-	return __uint_as_float(t[0]) + __uint_as_float(t[1]);
-}
 
 // Gaussians with MORE than GSR_SUM_LONG instance rows (a splat tens of pixels wide sits in hundreds of tile lists) are not
 // summed by their own lane -- one lane adding 400 rows while 63 wait made preprocess_bwd 4x slower on a scene with 1 % of
@@ -129,372 +113,36 @@ void launch_inspect_sums(int P, const int* radii, const GsRec* recs, const uint3
 }
 
 // ------------------------------------------------------------------------------------------------
-// composite_bwd: ONE workgroup of 4 wave64 per 16x16 tile; wave w owns the 8x8 pixel block w of the tile, one pixel
-// per lane -- the forward's layout (gs_pixel_of_thread), walked back to front.
+// composite_bwd (composite_bwd_quarter_kernel): ONE workgroup of 4 wave64 per 16x16 tile, one pixel per lane, walked back
+// to front.  Wave w owns the 8x8 pixel block w of the tile and every 16-lane quarter of it a 4x4 block -- the layout of
+// composite_fwd_quarter_kernel.  Instances are staged GSR_BWQ_BATCH at a time; every quarter walks its OWN list of the staged
+// instances, compacted from a per-instance 4-bit mask (the forward's block masks, or gs_quarter_mask<2> against the wave's
+// four blocks when the forward left none; cut by each quarter's own last_contributor bound).
 //
-// The expensive part of this kernel used to be the cross-lane reduction: every (wave, instance) pair has to turn 64
-// per-pixel contributions into ten per-Gaussian sums, and a lane-swap / DPP tree for ten quantities costs ~130 VALU
-// cycles per pair however it is arranged (rounds 1-2: 45 % of the kernel).  It is now done by TRANSPOSITION
-// through LDS instead:
-//   phase 1 (lane = pixel): per pair only the two per-pixel scalars everything else is linear in are computed,
+// Every (quarter, instance) pair has to turn 16 per-pixel contributions into ten per-Gaussian sums (by slot of the plane)
+//   0 M10 = sum q dx, 1 M01 = sum q dy, 2 M20, 3 M11, 4..6 sum w dL_dpixel[c], 7 sum w dL_ddepth, 8 M02, 9 sum (w dL_dopacity + q)
+// and a cross-lane reduction tree for ten quantities per pair costs more than everything else in the walk.  The sums are
+// formed by TRANSPOSITION through LDS instead:
+//   phase 1 (lane = pixel): list step i of all four quarters in one instruction stream.  Per step only the two per-pixel
+//           scalars everything else is linear in are computed,
 //           q = G * dL_dalpha   and   w = alpha * T_before,
-//           and stored as one 8-byte LDS write per lane into the pair's row of the wave's slab;
-//   phase 2 (lane = (pair u, pixel row g), every GSR_BWD_UNITS pairs): each lane walks the 8 pixels of ITS row of
-//           ITS pair and accumulates the ten sums with plain FMAs against per-pixel constants (upstream gradients
-//           from a small LDS table, dx / dy recomputed) -- 64 pixels x 10 FMAs = 10 wave-instructions per pair
-//           instead of a reduction tree; three swap / DPP steps fold the 8 rows (lanes of the same pair only).
-// No LDS float atomics, and the per-pixel products (q*dx, w*dL_dpixel, ...) leave phase 1 as well.  The four waves
-// write their sums into four private planes that the flush adds in a fixed order: gradients stay bit-reproducible
-// from run to run.
-// The median-depth gradient (backward.cu:566-569) goes to the Gaussian the FORWARD recorded as the pixel's median
-// (med_pos, same decision as forward.cu:368-373 on the forward's own transmittances): one integer compare per pixel
-// in phase 2.  The reference re-derives the crossing from a transmittance reconstructed by division, which is
-// ill-conditioned at the threshold; the two can only disagree inside the window tests/ grant as `flip9`.
-// Staging is software-pipelined: the records of the NEXT batch (and the ids of the one after) are requested before
-// the walk of the current one, four threads per 64-B record, so the dependent point_list -> record gathers are not
-// waited for between batches.
-// ------------------------------------------------------------------------------------------------
-#define GSR_BWD_THREADS 256
-#define GSR_BWD_BATCH 64      // instances staged per round: one lane-test per (wave, instance) in a single ballot
-#ifndef GSR_BWD_UNITS
-#define GSR_BWD_UNITS 8       // pairs per transposed reduction; lane = (pair u = lane % UNITS, pixel group g = lane / UNITS)
-#endif
-#define GSR_SLAB_STRIDE 65    // float2 per pair row: 64 pixels + 1 pad (conflict-free b64 reads across pairs)
-#define GSR_PLANE_STRIDE 10   // floats per instance in a wave's plane of sums
-#define GSR_TAB_ROW 17        // float4 per pixel row of the constants table: 8 pixels x 2 + 1 pad (rows on distinct banks)
-
-#ifdef GSR_AB_VARIANTS   // the per-wave (8x8) walk: superseded by the per-quarter kernel below, kept for A/B builds only (make AB=1)
-// Phase 2: the wave's slab holds (q, w) of `n` pairs; writes their ten sums into the wave's plane.
-//   sums: 0 M10 = sum q dx, 1 M01 = sum q dy, 2 M20, 3 M11, 4 M02, 5 sum (w dL_dopacity + q), 6..8 sum w dL_dpixel[c],
-//         9 sum w dL_ddepth + (median gradient of the pixels whose median this Gaussian is)
-// tab: per pixel (sx, row) two float4 at [row * GSR_TAB_ROW + 2 sx]: {dL_dpixel rgb, dL_ddepth}, {dL_dopacity,
-// dL_dmedian, med_pos bits, -}.
-__device__ __forceinline__ void gs_bwd_phase2(const int n, const float2* __restrict__ slab, const unsigned long long unit_js,
-                                              const float4* __restrict__ sA, const float4* __restrict__ tab, const float fbx,
-                                              const float fby, const int top, float* __restrict__ plane, const int lane)
-{
-	constexpr int NG = 64 / GSR_BWD_UNITS;      // pixel groups: 8 (one pixel row each) or 16 (half a row each)
-	constexpr int PPL = GSR_BWD_UNITS;          // pixels per lane
-	const int u = lane & (GSR_BWD_UNITS - 1), g = lane / GSR_BWD_UNITS;
-	const bool act = u < n;
-	// batch indices of the slab's pairs, 8 bits each, packed by phase 1 with scalar instructions (wave-uniform)
-	const int j = act ? (int)((unit_js >> (8 * u)) & 0xffull) : 0;
-	const float2 ctr = *reinterpret_cast<const float2*>(&sA[j]);   // Gaussian centre
-	const uint32_t pos1 = (uint32_t)(top - j);   // list position + 1 of the pair's instance
-	const int prow = NG == 8 ? g : (g >> 1), pcol0 = NG == 8 ? 0 : ((g & 1) << 2);   // first pixel of the lane's group
-	const float dy = ctr.y - (fby + (float)prow);
-	const float X = ctr.x - (fbx + (float)pcol0);          // dx of the lane's first pixel; dx of pixel sx is X - sx
-	const float2* row = slab + u * GSR_SLAB_STRIDE + prow * 8 + pcol0;
-	const float4* trow = tab + prow * GSR_TAB_ROW + 2 * pcol0;
-	// All pixels of a lane share dy, so dy factors out of M01, M11, M02 (exactly up to one rounding each, relative to
-	// the magnitude of the factored sum) and only sum q, sum q dx, sum q dx^2 are accumulated per pixel.
-	float S0 = 0.f, a0 = 0.f, a2 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f, a8 = 0.f, a9 = 0.f;
-#pragma unroll
-	for (int sx = 0; sx < PPL; sx++) {
-		const float2 v = row[sx];                           // (q, w) of the pixel
-		const float4 c0 = trow[2 * sx], c1 = trow[2 * sx + 1];
-		const float dx = X - (float)sx;
-		const float t = v.x * dx;
-		S0 += v.x;
-		a0 += t;
-		a2 = FMA(t, dx, a2);
-		a5 = FMA(v.y, c1.x, a5);                             // backward.cu:575 (+ :607 below: + sum q)
-		a6 = FMA(v.y, c0.x, a6);
-		a7 = FMA(v.y, c0.y, a7);
-		a8 = FMA(v.y, c0.z, a8);
-		a9 = FMA(v.y, c0.w, a9) + ((__float_as_uint(c1.z) == pos1) ? c1.y : 0.f);
-	}
-	a5 += S0;
-	const float a1 = dy * S0, a3 = dy * a0, a4 = dy * a1;
-	// fold the pixel groups of every pair: lanes u + UNITS * g (partners always belong to the same pair, so stale
-	// slab rows of inactive pairs never leak into active ones)
-	const float r0 = half_swap_sum(a0, a1);
-	const float r1 = half_swap_sum(a2, a3);
-	const float r2 = half_swap_sum(a4, a5);
-	const float r3 = half_swap_sum(a6, a7);
-	const float r4 = half_swap_sum(a8, a9);
-	float s0 = row_swap_sum(r0, r1), s1 = row_swap_sum(r2, r3), s2 = row_swap_sum(r4, 0.f);
-	GSR_DPP_ADD(s0, 0x128); GSR_DPP_ADD(s1, 0x128); GSR_DPP_ADD(s2, 0x128);   // row_ror:8: lanes l and l ^ 8
-	// UNITS == 4: lanes u + 4 k of a row still differ; after the previous step the values are symmetric under l ^ 8,
-	// so (l + 4) % 16 is as good as l ^ 4
-	if (NG == 16) { GSR_DPP_ADD(s0, 0x124); GSR_DPP_ADD(s1, 0x124); GSR_DPP_ADD(s2, 0x124); }   // row_ror:4
-	// 16-lane row r of s0 / s1 / s2 now holds component {0,2,1,3}[r] / 4+{0,2,1,3}[r] / {8,-,9,-}[r] of pair u
-	if (act && (lane & (16 - GSR_BWD_UNITS) & 15) == 0) {
-		const int rw = lane >> 4;
-		float* dst = plane + j * GSR_PLANE_STRIDE + (((rw & 1) << 1) | (rw >> 1));
-		dst[0] = s0;
-		dst[4] = s1;
-		if ((rw & 1) == 0) dst[8] = s2;
-	}
-}
-
-// FLAGS: long-list regime (per-row validity bytes); compile-time so that the short-list kernel carries none of it.
-// TSEL: keep a select on T for devices where v_rcp_f32(1.0) != 1.0 (gsr_selftest).
-template <bool FLAGS, bool TSEL>
-__global__ __launch_bounds__(GSR_BWD_THREADS) void composite_bwd_kernel(
-    int T, int chunk, int gx, int W, int H, const GsBg bgv, const uint2* __restrict__ ranges,
-    const uint32_t* __restrict__ point_list, const GsRec* __restrict__ recs, const uint32_t* __restrict__ goff,
-    const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ med_pos,
-    const float* __restrict__ dL_dpix, const float* __restrict__ dL_dpix_depth, const float* __restrict__ dL_dpix_median,
-    const float* __restrict__ dL_dpix_opacity, float* __restrict__ rows, uint8_t* __restrict__ row_flags,
-    const GsCtl* __restrict__ ctl)
-{
-	__shared__ float4 sA[GSR_BWD_BATCH];   // q0: px, py, -a/2, -b
-	__shared__ float4 sB[GSR_BWD_BATCH];   // q1: -c/2, opacity, depth, pcut
-	__shared__ float4 sC[GSR_BWD_BATCH];   // q2: r, g, b, -
-	__shared__ uint32_t s_row[GSR_BWD_BATCH];   // Gaussian-major row of each staged instance
-	__shared__ __attribute__((aligned(16))) float s_plane[4][GSR_BWD_BATCH * GSR_PLANE_STRIDE];   // per-wave sums of the batch
-	__shared__ float2 s_slab[4][GSR_BWD_UNITS * GSR_SLAB_STRIDE];
-	__shared__ float4 s_tab[4][8 * GSR_TAB_ROW];            // per-pixel constants of phase 2
-	__shared__ int s_max[4];
-	if (blockIdx.x == 0 && threadIdx.x == 0 && bgv.flag_dst != nullptr) *bgv.flag_dst = bgv.flag;   // regime word (GsBg)
-	// XCD-banded static order, or (skewed frames) longest walk first: launch_tile_order
-	// (a banded backward, GSR_BWD_PART_BAND_*, walks the tiles [tile_lo, tile_hi) only: the XCD bands are cut out of THAT range, so
-	// that a band still runs on all eight XCDs -- cut out of the whole image, the upper half of the tiles lives on four of them)
-	const int tb_lo = (int)bgv.tile_lo, tb_n = (int)min(bgv.tile_hi, (uint32_t)T) - tb_lo;
-	const int local = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-	const int tile = bgv.tile_order ? ((int)blockIdx.x < T ? (int)bgv.tile_order[blockIdx.x] : T) : tb_lo + local;
-	if ((!bgv.tile_order && ((int)(blockIdx.x >> 3) >= chunk || local >= tb_n)) || tile >= T) return;
-	if ((uint32_t)tile < bgv.tile_lo || (uint32_t)tile >= bgv.tile_hi) return;   // (longest-first order of a skewed frame: every tile is offered to both bands)
-	const int tid = threadIdx.x;
-	const int lane = tid & 63, wv = tid >> 6;
-	const int tx = tile % gx, ty = tile / gx;
-	int lx, ly;
-	gs_pixel_of_thread(tid, lx, ly);
-	const int px = tx * GSR_BLOCK_X + lx, py = ty * GSR_BLOCK_Y + ly;
-	const bool inside = px < W && py < H;
-	const float pixfx = (float)px, pixfy = (float)py;
-	// this wave's pixel block (pixel centres), clipped to the image
-	const float fbx = (float)(tx * GSR_BLOCK_X + ((wv & 1) << 3)), fby = (float)(ty * GSR_BLOCK_Y + ((wv >> 1) << 3));
-	const float bx1 = fminf(fbx + 7.f, (float)(W - 1)), by1 = fminf(fby + 7.f, (float)(H - 1));
-	const uint2 range = ranges[tile];
-
-	const size_t sidx = (size_t)tile * GSR_TILE_PIX + tid;   // the forward's tile-major pixel state
-	const float T_final = inside ? final_T[sidx] : 0.f;
-	const int lc = inside ? (int)n_contrib[sidx] : 0;          // last_contributor
-	float dLp0 = 0.f, dLp1 = 0.f, dLp2 = 0.f, dLd = 0.f, dLo = 0.f;
-	{
-		float dLm = 0.f;
-		uint32_t mpos = 0u;
-		if (inside) {
-			const size_t HW = (size_t)H * W;
-			const size_t pix_id = (size_t)W * py + px;
-			// an upstream gradient the caller did not supply (NULL: an output the loss does not use) is zero: not loaded
-			if (dL_dpix) {
-				dLp0 = dL_dpix[pix_id];
-				dLp1 = dL_dpix[HW + pix_id];
-				dLp2 = dL_dpix[2 * HW + pix_id];
-			}
-			if (dL_dpix_depth) dLd = dL_dpix_depth[pix_id];
-			if (dL_dpix_median) dLm = dL_dpix_median[pix_id];   // channel 0 only (backward.cu:481-482)
-			if (dL_dpix_opacity) dLo = dL_dpix_opacity[pix_id];
-			mpos = med_pos[sidx];
-		}
-		// lane = pixel (lx & 7, ly & 7) of the wave's block
-		float4* t = s_tab[wv] + (lane >> 3) * GSR_TAB_ROW + 2 * (lane & 7);
-		t[0] = make_float4(dLp0, dLp1, dLp2, dLd);
-		t[1] = make_float4(dLo, dLm, __uint_as_float(mpos), 0.f);
-	}
-	// bg . dL_dpixel (backward.cu:584-586), loop invariant
-	const float bg0 = bgv.dptr ? bgv.dptr[0] : bgv.host[0], bg1 = bgv.dptr ? bgv.dptr[1] : bgv.host[1], bg2 = bgv.dptr ? bgv.dptr[2] : bgv.host[2];
-	const float bg_dot = FMA(bg2, dLp2, FMA(bg1, dLp1, FMA(bg0, dLp0, 0.f)));
-	// wave-uniform: with a black background (the common case) the term is skipped by a scalar branch
-	const bool any_bg = __ballot(bg_dot != 0.f) != 0ull;
-	float T_ = T_final;
-	// The reference carries five back-to-front recurrences accum_rec[ch] (3 colours, depth, opacity;
-	// backward.cu:541-573) but dL_dalpha only needs their dot product with this pixel's upstream gradients, and the
-	// recurrence is linear: one scalar S = <accum_rec, dL_dpixel> is carried, updated EAGERLY with this Gaussian's
-	// alpha (the reference folds last_alpha / last_color in at the next contributor: the same fma one step later).
-	float S = 0.f;
-
-	// block / tile maxima of last_contributor: list entries at or beyond them are dead for every pixel
-	int wmax = lc;
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, __shfl_xor(wmax, o, 64));
-	wmax = __builtin_amdgcn_readfirstlane(wmax);
-	if (lane == 0) s_max[wv] = wmax;
-	__syncthreads();
-	const int bmax = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-
-	// List entries at or beyond bmax contribute to no pixel of this tile.  Two regimes, chosen by the launcher from
-	// the average list length:
-	//   short lists (most of a list is walked): their rows are zeroed here, under the shadow of the main loop, and
-	//     preprocess_bwd adds every row unconditionally;
-	//   long lists (real scenes: a few thousand entries of which ~15 % are reached): row_flags != nullptr -- written
-	//     rows set a validity byte, unreached entries are left alone and preprocess_bwd skips them WITHOUT reading
-	//     them (clearing + re-reading 48 B per unreached entry was the larger cost: C4 share 1.42 -> 0.59 ms here).
-	for (int i = bmax + tid; !FLAGS && i < (int)(range.y - range.x); i += GSR_BWD_THREADS) {
-		const uint32_t id = point_list[range.x + i];
-		const uint4 q3 = recs[id].q3;
-		float4* dst = reinterpret_cast<float4*>(rows + (size_t)(goff[id] + gs_row_in_rect(q3.x, q3.y, (q3.z >> GSR_Q3Z_DEAD_SHIFT) & 15u, tx, ty)) * GSR_ROW_STRIDE);
-		dst[0] = make_float4(0.f, 0.f, 0.f, 0.f);
-		dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-		dst[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-	}
-	float2* slab = s_slab[wv];
-	float* plane = s_plane[wv];
-	// ---- software-pipelined staging: thread t fetches 16-B part (t & 3) of the record of staged instance t >> 2 ----
-	const int srec = tid >> 2, spart = tid & 3;
-	auto load_id = [&](int t) -> uint32_t {   // id of list position t-1-srec (0 when outside the walk)
-		return (t > 0 && srec < min(GSR_BWD_BATCH, t)) ? point_list[range.x + (uint32_t)(t - 1 - srec)] : 0u;
-	};
-	// part 3 (q3: tile rect) also fetches the Gaussian's first row goff[id] into the unused .w
-	auto load_part = [&](int t, uint32_t id) -> float4 {
-		float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-		if (t > 0 && srec < min(GSR_BWD_BATCH, t)) {
-			v = reinterpret_cast<const float4*>(recs + id)[spart];
-			if (spart == 3) v.w = __uint_as_float(goff[id]);
-		}
-		return v;
-	};
-	uint32_t id_next = load_id(bmax - GSR_BWD_BATCH);
-	float4 part_cur = load_part(bmax, load_id(bmax));
-	// walk positions pos = bmax-1 ... 0, staged GSR_BWD_BATCH at a time
-	for (int top = bmax; top > 0; top -= GSR_BWD_BATCH) {
-		const int cnt = min(GSR_BWD_BATCH, top);
-		__syncthreads();   // the previous flush has read sA / sB / the planes
-		if (srec < cnt) {
-			if (spart == 0) sA[srec] = part_cur;
-			else if (spart == 1) sB[srec] = part_cur;
-			else if (spart == 2) sC[srec] = part_cur;
-			else {
-				// Gaussian-major row of this (tile, Gaussian) instance: goff[g] (fetched with the record) + raster index
-				// of the tile inside the Gaussian's tile rect
-				const uint32_t q3x = __float_as_uint(part_cur.x), q3y = __float_as_uint(part_cur.y), q3w = __float_as_uint(part_cur.w);
-				s_row[srec] = q3w + gs_row_in_rect(q3x, q3y, (__float_as_uint(part_cur.z) >> GSR_Q3Z_DEAD_SHIFT) & 15u, tx, ty);
-			}
-		}
-		// request the next batch's records and the ids of the one after: in flight during this batch's walk
-		const float4 part_next = load_part(top - GSR_BWD_BATCH, id_next);
-		id_next = load_id(top - 2 * GSR_BWD_BATCH);
-		// zero the four planes of sums (4 x 64 x 10 floats = 640 float4)
-		for (int i = tid; i < 4 * GSR_BWD_BATCH * GSR_PLANE_STRIDE / 4; i += GSR_BWD_THREADS)
-			reinterpret_cast<float4*>(&s_plane[0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-		__syncthreads();
-		// per-wave cull of the staged batch: lane l tests instance l against the wave's pixel block (see composite_fwd)
-		bool hit = false;
-		if (lane < cnt && top - 1 - lane < wmax) hit = gs_box_may_touch(sA[lane], sB[lane], fbx, fby, bx1, by1);
-		unsigned long long m = __ballot(hit);
-		int nu = 0;        // pairs in the slab (wave-uniform)
-		unsigned long long unit_js = 0ull;   // batch indices of the slab's pairs, 8 bits each (wave-uniform: SGPRs)
-		// one (wave, instance) pair; returns with the pair's (q, w) in the slab, or without a trace if no pixel is live
-		auto pair = [&](const float4 A, const float4 B, const float4 Cc, const int j) {
-			const int pos = top - 1 - j;   // == `contributor` after decrement (backward.cu:520)
-			const float dx = A.x - pixfx, dy = A.y - pixfy;
-			const float power = FMA(A.w * dx, dy, FMA(B.x * dy, dy, (A.z * dx) * dx));
-			const float G = gs_exp(power);
-			const float a0 = B.y * G;
-			// no short-circuit evaluation: `&` keeps the body free of exec-mask branches
-			const bool live = (pos < lc) & (power <= 0.0f) & (power >= B.w) & (!(a0 < 1.0f / 255.0f));
-			if (__ballot(live) == 0ull) return;
-			// a dead pixel is carried through with G masked to 0, which makes everything derived from it exactly
-			// neutral: alpha = 0, 1/(1-alpha) = 1 (v_rcp_f32(1.0) == 1.0, gsr_selftest), w = 0, q = 0, S <- fma(0,.,S)
-			const float Gm = live ? G : 0.f;
-			const float alpha = fminf(0.99f, B.y * Gm);
-			// 1/(1-alpha) once, by v_rcp_f32 (1 ulp) instead of two IEEE divisions (backward.cu:536,587): the backward
-			// is tolerance-checked (its sums are order-dependent in the reference as well)
-			const float rinv = __builtin_amdgcn_rcpf(1.0f - alpha);
-			const float test_T = T_ * rinv;
-			const float w = alpha * test_T;   // dchannel_dcolor = dpixel_depth_ddepth = dpixel_opacity_dopacity
-			// <colour of this Gaussian, dL_dpixel> over the 5 blended channels (rgb, depth, opacity == 1)
-			const float cd = FMA(Cc.x, dLp0, FMA(Cc.y, dLp1, FMA(Cc.z, dLp2, FMA(B.z, dLd, dLo))));
-			const float diff = cd - S;
-			float dL_dalpha = diff * test_T;
-			if (any_bg) {                                                         // backward.cu:584-587
-				asm volatile("");   // not speculated: keeps this a scalar branch instead of compute-always + select
-				dL_dalpha = FMA(-(T_final * rinv), bg_dot, dL_dalpha);
-			}
-			const float q = Gm * dL_dalpha;                                       // dL_dG * G / opacity
-			S = FMA(alpha, diff, S);
-			T_ = TSEL ? (live ? test_T : T_) : test_T;
-			slab[nu * GSR_SLAB_STRIDE + lane] = make_float2(q, w);
-			unit_js |= (unsigned long long)j << (8 * nu);
-			nu++;
-			if (nu == GSR_BWD_UNITS) {
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier();
-				gs_bwd_phase2(GSR_BWD_UNITS, slab, unit_js, sA, s_tab[wv], fbx, fby, top, plane, lane);
-				__builtin_amdgcn_wave_barrier();
-				nu = 0;
-				unit_js = 0ull;
-			}
-		};
-		// the record of the NEXT surviving instance is read (wave-uniform LDS reads) while the current pair computes:
-		// two copies of the body alternate between two register sets instead of moving 12 registers per pair
-		if (m) {
-			int j0 = __ffsll((long long)m) - 1, j1 = 0;
-			m &= m - 1;
-			float4 A0 = sA[j0], B0 = sB[j0], C0 = sC[j0], A1, B1, C1;
-			while (true) {
-				const bool more1 = m != 0ull;
-				if (more1) {
-					j1 = __ffsll((long long)m) - 1;
-					m &= m - 1;
-					A1 = sA[j1]; B1 = sB[j1]; C1 = sC[j1];
-				}
-				pair(A0, B0, C0, j0);
-				if (!more1) break;
-				const bool more0 = m != 0ull;
-				if (more0) {
-					j0 = __ffsll((long long)m) - 1;
-					m &= m - 1;
-					A0 = sA[j0]; B0 = sB[j0]; C0 = sC[j0];
-				}
-				pair(A1, B1, C1, j1);
-				if (!more0) break;
-			}
-		}
-		if (nu > 0) {
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			gs_bwd_phase2(nu, slab, unit_js, sA, s_tab[wv], fbx, fby, top, plane, lane);
-		}
-		// flush: one thread per staged instance adds the four planes in fixed order and stores the 48-B row (plain
-		// stores, no global atomics), zeros included: every row of the scratch is written exactly once per backward,
-		// so nobody has to clear it
-		__syncthreads();
-		if (tid < cnt) {
-			float v[10];
-#pragma unroll
-			for (int k = 0; k < 10; k++)
-				v[k] = ((s_plane[0][tid * GSR_PLANE_STRIDE + k] + s_plane[1][tid * GSR_PLANE_STRIDE + k]) +
-				        s_plane[2][tid * GSR_PLANE_STRIDE + k]) + s_plane[3][tid * GSR_PLANE_STRIDE + k];
-			// moments -> gradients (once per (tile, Gaussian)): with q = G*dL_dalpha summed over pixels,
-			//   dL_dmean2D.x = -0.5W * op * (a*M10 + b*M01)      (backward.cu:593-599)
-			//   dL_dconic    = -0.5 * op * (M20, M11, M02)       (backward.cu:602-604)
-			// where conic (a, b, c) = (-2*q0.z, -q0.w, -2*q1.x), op = q1.y
-			const float4 A = sA[tid], B = sB[tid];
-			const float ca = -2.f * A.z, cb = -A.w, cc = -2.f * B.x, op = B.y;
-			const float M10 = v[0], M01 = v[1], M20 = v[2], M11 = v[3], M02 = v[4];
-			const float ddelx_dx = (float)(0.5 * W), ddely_dy = (float)(0.5 * H);   // backward.cu:493-494
-			const uint32_t my_row = s_row[tid];
-			float4* dst = reinterpret_cast<float4*>(rows + (size_t)my_row * GSR_ROW_STRIDE);
-			dst[0] = make_float4(-(op * FMA(cb, M01, ca * M10)) * ddelx_dx, -(op * FMA(cb, M10, cc * M01)) * ddely_dy,
-			                     -0.5f * op * M20, -0.5f * op * M11);
-			dst[1] = make_float4(-0.5f * op * M02, v[5], v[6], v[7]);
-			dst[2] = make_float4(v[8], v[9], 0.f, 0.f);
-			if (FLAGS) row_flags[my_row] = 1;
-		}
-		part_cur = part_next;
-	}
-}
-
-#endif   // GSR_AB_VARIANTS
-
-// ------------------------------------------------------------------------------------------------
-// composite_bwd with per-quarter instance lists (the default; the kernel above is kept as variant bit 1 for A/B).
-// Same transposition idea, finer granularity -- the forward's (composite_fwd_quarter_kernel): every 16-lane quarter
-// of a wave owns a 4x4 pixel block and walks its OWN list of the staged instances, compacted from a per-instance
-// 4-bit mask (gs_quarter_mask<2> against the wave's four blocks, cut by each quarter's own last_contributor bound).
-//   phase 1 (lane = pixel): list step i of all four quarters in one instruction stream; (q, w) go to the slab row of
-//           (quarter, step);
+//           and stored as one 8-byte LDS write per lane into the slab row of (quarter, step); the per-pixel products
+//           (q*dx, w*dL_dpixel, ...) leave phase 1;
 //   phase 2 (every GSR_BWQ_U steps; lane = (quarter, step u, pixel row r)): the lane accumulates the 4 pixels of its
-//           row -- their upstream gradients live in REGISTERS (20 VGPRs; with 8 pixels per lane they had to be
-//           re-read from an LDS table for every pair: 80 % of phase 2's LDS traffic), folds the 4 rows with two DPP
-//           butterflies and adds the ten sums to the instance's slot in the wave's plane.  Quarters of a wave may
+//           row with plain FMAs (dx / dy recomputed from the centre) -- their upstream gradients live in REGISTERS (20 VGPRs;
+//           re-read from an LDS table for every pair they were 80 % of phase 2's LDS traffic) --, folds the 4 rows with two DPP
+//           exchanges and adds the ten sums to the instance's slot in the wave's plane.  Quarters of a wave may
 //           meet in an instance, so the four quarters take turns with plain read / add / write around the steps of
-//           the NEXT group (program order between the turns, the read's latency hidden behind a step); across waves
-//           there are four planes, added by the flush in fixed order as before: bit-reproducible from run to run.
+//           the NEXT group (program order between the turns, the read's latency hidden behind a step).
+// Each wave has a PRIVATE plane of sums (GSR_PLANE_STRIDE floats per staged instance), and the flush at the end of a round adds
+// the four planes in a fixed order, ((p0 + p1) + p2) + p3, turns the moments into gradients and stores one 48-B row per
+// (tile, Gaussian) instance in Gaussian-major order: plain stores, no global atomics, gradients bit-reproducible from run to run.
+// The median-depth gradient (backward.cu:566-569) goes to the Gaussian the FORWARD recorded as the pixel's median
+// (med_pos, same decision as forward.cu:368-373 on the forward's own transmittances).  The reference re-derives the crossing
+// from a transmittance reconstructed by division, which is ill-conditioned at the threshold; the two can only disagree inside
+// the window tests/ grant as `flip9`.  It is one Gaussian per pixel: added once per pixel, by an LDS float atomic on the wave's
+// own plane before the walk of the batch that position falls into (the only float atomic of the kernel; none on HBM).
+// A wave walks max over its quarters (C3: 0.73x the steps of a walk by whole 8x8 blocks), and phase 2 touches only hit quarters.
 //   Measured and not kept: LDS float atomics for the plane update (they serialise their lanes: 1.13 ms, the LDS pipe
 //   2.4x as busy); 8 steps per reduction with 8 pixels per lane (halves the fold, needs 165 VGPRs: 0.68 ms at 3
 //   waves/SIMD against 0.59 ms at 4); one float4 per lane and turn instead of three floats (spills: 0.69 ms); a fused
@@ -528,10 +176,10 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) void composite_bwd_kernel(
 //   form above is NOT cheaper on this pipe (read b128 4 + write b128 13 = 17, and it spilled).  A cheaper form exists and is small:
 //   with the three sums of a lane in adjacent words of the slot (a permutation of the plane's ten words, undone by the flush; the
 //   additions and their order stay) a turn is read b64 + b32, write b64 + b32 = 2 + 2 + 6 + 4 = 14, two cycles of 35 less.  Not built.
-// A wave walks max over its quarters (C3: 0.73x the steps of the 8x8 walk), and phase 2 touches only hit quarters.
-// The median-depth gradient (one Gaussian per pixel, the list position the forward recorded) is added once per pixel,
-// by an LDS atomic before the walk of the batch that position falls into.
-#define GSR_BWQ_U 4          // list steps per transposed reduction
+// ------------------------------------------------------------------------------------------------
+#define GSR_BWD_THREADS 256
+#define GSR_PLANE_STRIDE 10   // floats per instance in a wave's plane of sums
+#define GSR_BWQ_U 4         // list steps per transposed reduction
 #ifndef GSR_BWQ_BATCH
 #define GSR_BWQ_BATCH 128    // instances staged per round (64 or 128): the four waves and their quarters re-synchronise
                              // once per round -- census at C3: 30.1 k workgroup steps at 64, 28.3 k at 128 (20.9 k ideal)
@@ -548,6 +196,9 @@ template <bool B> struct GsBool { static constexpr bool value = B; };
 #define GSR_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0F70)
 #define GSR_BWQ_QSTRIDE 66   // float2 per quarter in the slab: 4 steps x 16 pixels + 2 pad (16-B aligned, banks shifted)
 
+// FLAGS: long-list regime (per-row validity bytes, see "two regimes" in the kernel); compile-time so that the short-list
+// kernel carries none of it.
+// TSEL: keep a select on T for devices where v_rcp_f32(1.0) != 1.0 (gsr_selftest).
 // FX: exp on the transcendental unit (gs_exp_hw), after a forward that ran in fast_exp mode: same instruction, same
 // bits, same alpha >= 1/255 decisions as that forward.  (Measured at C3: 0.5108 -> 0.5084 ms -- nine VALU instructions
 // fewer per step, but v_exp_f32 issues at a quarter of their rate; a third mode -- hardware exp after a
@@ -663,7 +314,11 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 	const float bg_dot = FMA(bg2, dLp2, FMA(bg1, dLp1, FMA(bg0, dLp0, 0.f)));
 	const bool any_bg = __ballot(bg_dot != 0.f) != 0ull;
 	float T_ = T_final;
-	float S = 0.f;   // <accum_rec, dL_dpixel>, see composite_bwd_kernel
+	// The reference carries five back-to-front recurrences accum_rec[ch] (3 colours, depth, opacity;
+	// backward.cu:541-573) but dL_dalpha only needs their dot product with this pixel's upstream gradients, and the
+	// recurrence is linear: one scalar S = <accum_rec, dL_dpixel> is carried, updated EAGERLY with this Gaussian's
+	// alpha (the reference folds last_alpha / last_color in at the next contributor: the same fma one step later).
+	float S = 0.f;
 
 	// quarter / block / tile maxima of last_contributor: list entries at or beyond them are dead there
 	int qmax = lc;
@@ -725,8 +380,13 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			if (spart >= 2) part[h].w = __uint_as_float(*word_ptr(bmax, h, id_cur[h]));
 		}
 	}
-	// rows of list entries no pixel of the tile reaches (short-list regime; see composite_bwd_kernel): their dependent chain
-	// (id -> record, first row -> stores) runs under the staging chain requested above
+	// List entries at or beyond bmax contribute to no pixel of this tile.  Two regimes, chosen by the launcher from
+	// the average list length:
+	//   short lists (most of a list is walked): their rows are zeroed here and preprocess_bwd adds every row unconditionally
+	//     -- the dependent chain (id -> record, first row -> stores) runs under the staging chain requested above;
+	//   long lists (real scenes: a few thousand entries of which ~15 % are reached): FLAGS, row_flags != nullptr -- written
+	//     rows set a validity byte, unreached entries are left alone and preprocess_bwd skips them WITHOUT reading
+	//     them (clearing + re-reading 48 B per unreached entry was the larger cost: C4 share 1.42 -> 0.59 ms here).
 	for (int i = bmax + tid; !FLAGS && i < (int)(range.y - range.x); i += GSR_BWD_THREADS) {
 		const uint32_t id = tile_list[i];
 		const uint4 q3 = recs[id].q3;
@@ -883,14 +543,17 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			// 1/(1-alpha) = 1 (gsr_selftest), w = 0, q = 0, S <- fma(0, ., S)
 			const float Gm = live ? G : 0.f;
 			const float alpha = fminf(0.99f, B.y * Gm);
+			// 1/(1-alpha) once, by v_rcp_f32 (1 ulp) instead of two IEEE divisions (backward.cu:536,587): the backward
+			// is tolerance-checked (its sums are order-dependent in the reference as well)
 			const float rinv = __builtin_amdgcn_rcpf(1.0f - alpha);
 			const float test_T = T_ * rinv;
-			const float w = alpha * test_T;
+			const float w = alpha * test_T;   // dchannel_dcolor = dpixel_depth_ddepth = dpixel_opacity_dopacity
+			// <colour of this Gaussian, dL_dpixel> over the 5 blended channels (rgb, depth, opacity == 1)
 			const float cd = FMA(Cc.x, dLp0, FMA(Cc.y, dLp1, FMA(Cc.z, dLp2, CONLY ? 0.f : FMA(B.z, dLd, dLo))));   // CONLY: dLd = dLo = 0, depth >= 0: that FMA is +0
 			const float diff = cd - S;
 			float dL_dalpha = diff * test_T;
 			if (decltype(BG)::value) dL_dalpha = FMA(-(T_final * rinv), bg_dot, dL_dalpha);   // backward.cu:584-587
-			const float q = Gm * dL_dalpha;
+			const float q = Gm * dL_dalpha;                                       // dL_dG * G / opacity
 			S = FMA(alpha, diff, S);
 			T_ = TSEL ? (live ? test_T : T_) : test_T;
 			my_slab_w[16 * st] = make_float2(q, w);
@@ -996,8 +659,8 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			phase2(cur, i);                                                                                                 \
 			__builtin_amdgcn_wave_barrier();                                                                                \
 		}
-		// (requesting the record of step k + 1 before evaluating step k -- two alternating register sets, what bought
-		// 7 % in the per-wave kernel -- changes nothing here: measured 0.528 against 0.527 ms)
+		// (requesting the record of step k + 1 before evaluating step k, in two alternating register sets, changes nothing:
+		// measured 0.528 against 0.527 ms)
 		if (any_bg) {
 			GSR_BWQ_WALK(GsBool<true>{})
 		} else {
@@ -1010,7 +673,9 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			turn_read(qq);
 			turn_write(qq);
 		}
-		// flush: one thread per staged instance adds the four planes in fixed order and stores the 48-B row
+		// flush: one thread per staged instance adds the four planes in fixed order and stores the 48-B row (plain
+		// stores, no global atomics), zeros included: every row of the scratch that the walk reaches is written exactly
+		// once per backward, so nobody has to clear it
 		TM(9)
 		GSR_WAIT_VM0();   // the loads requested at the top of the round have had the whole walk: arrived before the row stores are issued
 		__syncthreads();
@@ -1021,6 +686,10 @@ __global__ __launch_bounds__(GSR_BWD_THREADS) __attribute__((amdgpu_waves_per_eu
 			for (int k = 0; k < 10; k++)
 				v[k] = ((s_plane[0][fj * GSR_PLANE_STRIDE + k] + s_plane[1][fj * GSR_PLANE_STRIDE + k]) +
 				        s_plane[2][fj * GSR_PLANE_STRIDE + k]) + s_plane[3][fj * GSR_PLANE_STRIDE + k];
+			// moments -> gradients (once per (tile, Gaussian)): with q = G*dL_dalpha summed over pixels,
+			//   dL_dmean2D.x = -0.5W * op * (a*M10 + b*M01)      (backward.cu:593-599)
+			//   dL_dconic    = -0.5 * op * (M20, M11, M02)       (backward.cu:602-604)
+			// where conic (a, b, c) = (-2*sA.z, -sA.w, -2*sB.x), op = sB.y
 			const float4 A = sA[fj], B = sB[fj];
 			const float ca = -2.f * A.z, cb = -A.w, cc = -2.f * B.x, op = B.y;
 			const float M10 = v[0], M01 = v[1], M20 = v[2], M11 = v[3], M02 = v[8];
@@ -1113,25 +782,16 @@ void launch_composite_bwd(const ImgLayout& il, int W, int H, const GsBg& bg, con
                           const uint32_t* point_list, const GsRec* recs, const uint32_t* goff, const float* final_T,
                           const uint32_t* n_contrib, const uint32_t* med_pos, const float* dL_dpix, const float* dL_dpix_depth,
                           const float* dL_dpix_median, const float* dL_dpix_opacity, float* rows, uint8_t* row_flags,
-                          const GsCtl* ctl, int variant, hipStream_t s)
+                          const GsCtl* ctl, bool tsel, bool fast_exp, hipStream_t s)
 {
 	const int tb_n = (int)std::min(bg.tile_hi, (uint32_t)il.T) - (int)bg.tile_lo;   // tiles of this call (a band, or all of them)
 	const int chunk = bg.tile_order ? (il.T + 7) / 8 : std::max(1, (tb_n + 7) / 8);      // (at least one workgroup: it stores the regime word)
-	const bool tsel = (variant & 1) != 0, wave_lists = (variant & 2) != 0;
-	const bool fx = (variant & 8) != 0;   // the forward ran in fast_exp mode (per-quarter kernels only)
+	const bool fx = fast_exp;   // the forward ran in fast_exp mode
 	const bool flags = row_flags != nullptr;
 #define GSR_LAUNCH_CB(...)                                                                                         \
 	hipLaunchKernelGGL((__VA_ARGS__), dim3(chunk * 8), dim3(GSR_BWD_THREADS), 0, s, il.T, chunk, il.gx, W, H, bg,  \
 	                   ranges, point_list, recs, goff, final_T, n_contrib, med_pos, dL_dpix, dL_dpix_depth, dL_dpix_median, \
 	                   dL_dpix_opacity, rows, row_flags, ctl)
-#ifdef GSR_AB_VARIANTS
-	if (wave_lists) {
-		if (flags) { if (tsel) GSR_LAUNCH_CB(composite_bwd_kernel<true, true>); else GSR_LAUNCH_CB(composite_bwd_kernel<true, false>); }
-		else { if (tsel) GSR_LAUNCH_CB(composite_bwd_kernel<false, true>); else GSR_LAUNCH_CB(composite_bwd_kernel<false, false>); }
-	} else
-#else
-	(void)wave_lists;   // refused by gsr_backward in a build without GSR_AB_VARIANTS
-#endif
 	if (dL_dpix_depth == nullptr && dL_dpix_median == nullptr && dL_dpix_opacity == nullptr && !tsel) {
 		// colour-only loss: the specialised instantiation (a device that needs TSEL takes the general kernel, which treats NULL as zero)
 		if (fx) { if (flags) GSR_LAUNCH_CB(composite_bwd_quarter_kernel<true, false, true, true>); else GSR_LAUNCH_CB(composite_bwd_quarter_kernel<false, false, true, true>); }

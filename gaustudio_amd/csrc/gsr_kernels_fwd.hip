@@ -13,7 +13,8 @@
 //                    longer than 1024 keys
 //                    (replaces the global 45..47-bit cub::DeviceRadixSort, rasterizer_impl.cu:306-311)
 //   composite_fwd    one workgroup (4 waves, one 8x8 pixel block each) per 16x16 tile, front-to-back alpha
-//                    compositing with per-wave ballot culling (replaces forward.cu:261-397 renderCUDA)
+//                    compositing; every 16-lane quarter of a wave (a 4x4 block) walks its own culled list
+//                    (replaces forward.cu:261-397 renderCUDA)
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -1789,169 +1790,30 @@ void launch_tile_sort(int T, bool with_short, int long_level, const uint2* range
 
 
 // ------------------------------------------------------------------------------------------------
-// composite_fwd: 256 threads = 4 wave64; wave w owns one 8x8 pixel block of the tile (gs_pixel_of_thread).
-// Instances are staged 256 at a time through LDS as three float4 planes.  Each wave then culls the
-// staged list for ITS block 64 instances at a time: lane l tests instance l against the block's box
-// (gs_box_may_touch), the ballot is the list of instances worth evaluating, and the wave walks its set
-// bits in order (s_ff1) reading the records with wave-uniform (broadcast) ds_read_b128.  In the C3
-// scene ~3/4 of the (wave, instance) pairs die in the ballot at ~0.5 VALU op per pixel instead of ~20.
-// Per-lane early termination (`done`); a wave stops when all its lanes are done, the workgroup when
-// all four waves are.
+// composite_fwd (composite_fwd_quarter_kernel): 256 threads = 4 wave64 per 16x16 tile, one pixel per lane; wave w owns one
+// 8x8 pixel block of the tile and every 16-lane quarter of it a 4x4 block.
+// Instances are staged 256 at a time through LDS as three float4 planes: A = q0 of the record, B = {-0.5c, op, id, pcut},
+// C = {r, g, b, depth} -- the four blended channels sit in one aligned register quad, so the accumulation is two packed FMAs.
+// Every quarter walks ITS OWN list of the staged instances: the staging thread, which holds the record in registers anyway,
+// tests it against the tile's sixteen 4x4 blocks at once (gs_quarter_mask<4>, conservative: a cull removes work and changes no
+// bit), each wave compacts the four lists of its quarters (ballot + mbcnt) and the walk then takes list entry i of every quarter
+// in the same instruction -- records come from LDS with per-quarter addresses, which a b128 read serves in its four
+// 16-lane passes at no extra cost.  A wave walks max over its quarters (0.725x the iterations of a walk by whole 8x8 blocks
+// at C3, where only about half of the lanes of a hit block are live; census: tools/scene_stats.py), quarters re-synchronise
+// once per 256-instance batch.  Exhausted quarters read a sentinel record of opacity 0.
+// The step is straight-line predicated code (no per-test branches, no short-circuit evaluation: lanes rarely agree, so
+// branches would almost never be wave-uniformly skippable).  A skipped pair contributes with weight exactly 0:
+// fma(c, 0, acc) == acc for finite c, so one select on the weight replaces four on the accumulators.
+// Per-lane early termination (`done`); a wave stops when all its lanes are done (tested every eight groups of steps: a test
+// per step costs more than the tail it saves), the workgroup when all four waves are.
+// Median depth (forward.cu:368-373): the walk keeps a candidate -- list position and transmittance in front of the LAST applied
+// instance that saw T > 0.5; whether it really crossed 0.5, and its depth / weight / id, is settled once per pixel after the
+// walk, with alpha recomputed by the very operations of the walk: the bit pattern the walk would have kept.
 // XCD-aware tile order: workgroup b runs on XCD b%8 (observed placement, speed only); each XCD is
 // given a contiguous band of tiles so that neighbouring tiles, which share Gaussians, gather the
 // same records from the same 4 MiB L2.
-// NOCULL (debugging / parity A/B, gsr_set_option("cull", 0)): every staged instance is evaluated by every wave and
+// NOCULL (debugging / parity A/B, gsr_set_option("cull", 0)): every staged instance is on every quarter's list and
 // the pcut pre-test is replaced by the domain bound of gs_exp -- the culling must not change a single bit.
-#ifdef GSR_AB_VARIANTS   // the per-wave (8x8) walk: superseded by the per-quarter kernel below, kept for A/B builds only (make AB=1)
-template <bool NOCULL>
-__global__ __launch_bounds__(256) void composite_fwd_kernel(
-    int T, int chunk, int gx, int W, int H, const uint2* __restrict__ ranges,
-    const uint32_t* __restrict__ point_list, const GsRec* __restrict__ recs, float* __restrict__ out_color,
-    float* __restrict__ out_depth, float* __restrict__ out_median, float* __restrict__ out_opacity,
-    float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ med_pos_out,
-    const GsCtl* __restrict__ ctl, uint32_t cap, uint32_t max_sorted, const uint32_t* __restrict__ tile_order,
-    uint32_t* __restrict__ staged_out)
-{
-	__shared__ float4 sA[256];
-	__shared__ float4 sB[256];
-	__shared__ float4 sC[256];
-	// launched ahead of the host's read-back (see bin_scatter_kernel): leave when the binning buffer was too small or
-	// a list is longer than what the sort kernels launched with this call handle (its point_list is not written)
-	if (ctl->num_binned > cap || ctl->max_tile_count > max_sorted) return;
-	// XCD-banded static order, or (skewed frames) longest list first: launch_tile_order_fwd
-	const int tile = tile_order ? ((int)blockIdx.x < T ? (int)tile_order[blockIdx.x] : T) : (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-	if ((!tile_order && (int)(blockIdx.x >> 3) >= chunk) || tile >= T) return;
-	const int tid = threadIdx.x;
-	const int lane = tid & 63;
-	const int tx = tile % gx, ty = tile / gx;
-	int lx, ly;
-	gs_pixel_of_thread(tid, lx, ly);
-	const int px = tx * GSR_BLOCK_X + lx, py = ty * GSR_BLOCK_Y + ly;
-	const bool inside = px < W && py < H;
-	const float pixfx = (float)px, pixfy = (float)py;
-	// this wave's pixel box (pixel centres), clipped to the image
-	const float bx0 = (float)(tx * GSR_BLOCK_X + (((tid >> 6) & 1) << 3));
-	const float by0 = (float)(ty * GSR_BLOCK_Y + (((tid >> 6) >> 1) << 3));
-	const float bx1 = fminf(bx0 + 7.f, (float)(W - 1)), by1 = fminf(by0 + 7.f, (float)(H - 1));
-	const uint2 range = ranges[tile];
-	const int total = (int)(range.y - range.x);
-	bool done = !inside;
-	float T_ = 1.0f;
-	uint32_t last_contributor = 0;
-	v2f acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};   // (R, G), (B, depth)
-	// median candidate: list position (+1) and transmittance in front of the LAST applied instance that saw
-	// T > 0.5; whether it really crossed 0.5 -- and its depth / weight / id -- is settled once per pixel after
-	// the walk (two selects and one compare per pair instead of three and two)
-	uint32_t med_pos = 0;
-	float med_T = 0.f;
-
-	int staged = 0;   // instances this workgroup staged before every pixel of the tile had saturated (one store at the end: the bench's byte count)
-	for (int base = 0; base < total; base += 256) {
-		if (__syncthreads_and(done)) break;
-		const int cnt = min(256, total - base);
-		staged += cnt;
-		if (tid < cnt) {
-			const uint32_t id = point_list[range.x + base + tid];
-			const GsRec* r = recs + id;
-			sA[tid] = r->q0;
-			// staged planes: B = {-0.5c, op, id, pcut}, C = {r, g, b, depth}: the four blended channels sit in one
-			// aligned register quad, so the accumulation is two packed FMAs
-			float4 b = r->q1;
-			float4 c = r->q2;
-			c.w = b.z;
-			b.z = __int_as_float((int)id);
-			sB[tid] = b;
-			sC[tid] = c;
-		}
-		__syncthreads();
-		for (int sub = 0; sub < cnt; sub += 64) {
-			if (__ballot(!done) == 0ull) break;   // every pixel of this wave has saturated
-			const int jl = sub + lane;
-			bool hit = false;
-			if (jl < cnt) hit = NOCULL ? true : gs_box_may_touch(sA[jl], sB[jl], bx0, by0, bx1, by1);
-			unsigned long long m = __ballot(hit);
-			// walk the surviving instances in list order; the body is straight-line predicated code (no
-			// per-test branches, no short-circuit evaluation: within a hit block about half of the lanes are
-			// live, so branches would almost never be wave-uniformly skippable); records come from LDS with
-			// wave-uniform reads.
-			while (m) {
-				const int j = sub + __ffsll((long long)m) - 1;
-				m &= m - 1;
-				const float4 A = sA[j], B = sB[j], Cc = sC[j];
-				const float dx = A.x - pixfx, dy = A.y - pixfy;
-				// power = -0.5(a dx^2 + c dy^2) - b dx dy with pre-scaled conic (forward.cu:338)
-				const float power = FMA(A.w * dx, dy, FMA(B.x * dy, dy, (A.z * dx) * dx));
-				const float alpha = fminf(0.99f, B.y * gs_exp(power));
-				// forward.cu:339 (+ pcut), :346
-				const bool valid = (!done) & (power <= 0.0f) & (power >= (NOCULL ? -80.0f : B.w)) & (!(alpha < 1.0f / 255.0f));
-				const float test_T = T_ * (1 - alpha);
-				const bool stop = valid & (test_T < 0.0001f);                        // forward.cu:357-361
-				done = done | stop;
-				const bool apply = valid & (!stop);
-				// a skipped pair contributes with weight exactly 0: fma(c, 0, acc) == acc for finite c, so one select
-				// on the weight replaces four on the accumulators (results stay bit-identical)
-				const float w = apply ? alpha * T_ : 0.f;
-				acc01 = vfma(v2f{Cc.x, Cc.y}, v2f{w, w}, acc01);
-				acc23 = vfma(v2f{Cc.z, Cc.w}, v2f{w, w}, acc23);
-				const bool medc = apply & (T_ > 0.5f);                               // forward.cu:368 (first half)
-				med_pos = medc ? (uint32_t)(base + j + 1) : med_pos;
-				med_T = medc ? T_ : med_T;
-				T_ = apply ? test_T : T_;
-				last_contributor = apply ? (uint32_t)(base + j + 1) : last_contributor;
-				// (no per-pair "whole wave saturated" test: it cost two VALU and a scalar dependency per pair, 0.035 ms
-				// at C3, to save at most the tail of one 64-instance batch; saturation is checked per batch above)
-			}
-		}
-	}
-	final_T[(size_t)tile * GSR_TILE_PIX + tid] = T_;
-	n_contrib[(size_t)tile * GSR_TILE_PIX + tid] = last_contributor;
-	uint32_t med_final = 0;   // list position (+1) of the median Gaussian, 0 = the transmittance never crossed 0.5
-	if (inside) {
-		// median depth / weight / id (forward.cu:368-373): the candidate crossed 0.5 iff its test_T < 0.5; alpha is
-		// recomputed with the very operations of the walk, so the result is the bit pattern the walk would have kept
-		float median_D = 15.0f, median_weight = 0.f;
-		int median_id = 0;
-		if (med_pos != 0) {
-			const uint32_t id = point_list[range.x + med_pos - 1];
-			const GsRec* r = recs + id;
-			const float4 A = r->q0, B = r->q1;
-			const float dx = A.x - pixfx, dy = A.y - pixfy;
-			const float power = FMA(A.w * dx, dy, FMA(B.x * dy, dy, (A.z * dx) * dx));
-			const float alpha = fminf(0.99f, B.y * gs_exp(power));
-			if (med_T * (1 - alpha) < 0.5f) {
-				median_D = B.z;
-				median_weight = alpha * med_T;
-				median_id = (int)id;
-				med_final = med_pos;
-			}
-		}
-		const size_t HW = (size_t)H * W;
-		const size_t pix_id = (size_t)W * py + px;
-		out_color[pix_id] = acc01.x;
-		out_color[HW + pix_id] = acc01.y;
-		out_color[2 * HW + pix_id] = acc23.x;
-		out_depth[pix_id] = acc23.y;
-		out_median[pix_id] = median_D;
-		out_median[HW + pix_id] = median_weight;
-		out_median[2 * HW + pix_id] = (float)median_id;
-		out_opacity[pix_id] = 1 - T_;
-	}
-	med_pos_out[(size_t)tile * GSR_TILE_PIX + tid] = med_final;
-	if (tid == 0 && staged_out != nullptr) staged_out[tile] = (uint32_t)staged;
-}
-
-#endif   // GSR_AB_VARIANTS
-
-// ------------------------------------------------------------------------------------------------
-// composite_fwd with per-quarter instance lists.  In the kernel above a wave (one 8x8 pixel block) walks every staged
-// instance that may touch its block, and within such a block only about half of the lanes are live.  Here every
-// 16-lane quarter of the wave owns a 4x4 pixel block and walks ITS OWN list of instances: the staging thread, which
-// holds the record in registers anyway, tests it against the tile's sixteen 4x4 blocks at once (gs_quarter_mask), each
-// wave compacts the four lists of its quarters (ballot + mbcnt) and the walk then takes list entry i of every quarter
-// in the same instruction -- records come from LDS with per-quarter addresses, which a b128 read serves in its four
-// 16-lane passes at no extra cost.  A wave walks max over its quarters instead of the 8x8 count: 0.725x the iterations
-// at C3 (census: tools/scene_stats.py), quarters re-synchronise once per 256-instance batch.  Exhausted quarters read a
-// sentinel record of opacity 0.  Per pixel the sequence of applied instances is unchanged: results are bit-identical.
 #define GSR_FWD_PLANE 257                      // records per staged plane (256 + the sentinel)
 #define GSR_FWD_SENT_OFF (256 * 16)            // byte offset of the sentinel record inside a plane
 #define GSR_FWD_LIST 264                       // list entries per quarter (u16 byte offsets): 256 + two groups of sentinels
@@ -1978,8 +1840,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_FWD_WAV
 	__shared__ float4 sRec[3 * GSR_FWD_PLANE];   // planes A, B, C (as above), slot 256 of each = the sentinel
 	__shared__ uint16_t sMask[256];
 	__shared__ __attribute__((aligned(16))) uint16_t sList[4][4][GSR_FWD_LIST];
+	// launched ahead of the host's read-back (see bin_scatter_kernel): leave when the binning buffer was too small or
+	// a list is longer than what the sort kernels launched with this call handle (its point_list is not written)
 	const uint32_t num_binned = ctl->num_binned;
-	if (num_binned > cap || ctl->max_tile_count > max_sorted) return;   // see composite_fwd_kernel
+	if (num_binned > cap || ctl->max_tile_count > max_sorted) return;
 	// the block masks computed below stay behind for composite_bwd (gs_qmask_ptr)
 	uint16_t* __restrict__ qmask = gs_qmask_ptr(point_list, num_binned);
 	if (!NOCULL && blockIdx.x == 0 && threadIdx.x == 0) ctl->has_qmask = 1u;
@@ -2204,29 +2068,19 @@ void launch_tile_order_fwd(int T, const uint2* ranges, uint32_t* order, const Gs
 void launch_composite_fwd(const ImgLayout& il, int W, int H, const uint2* ranges, const uint32_t* point_list,
                           const GsRec* recs, float* out_color, float* out_depth, float* out_median,
                           float* out_opacity, float* final_T, uint32_t* n_contrib, uint32_t* med_pos,
-                          GsCtl* ctl_, uint32_t cap, uint32_t max_sorted, bool nocull, bool wave_lists, bool fast_exp,
+                          GsCtl* ctl, uint32_t cap, uint32_t max_sorted, bool nocull, bool fast_exp,
                           const uint32_t* tile_order, uint32_t* staged_out, hipStream_t s)
 {
 	const int chunk = (il.T + 7) / 8;
 #define GSR_LAUNCH_FWD(K)                                                                                              \
 	hipLaunchKernelGGL(K, dim3(chunk * 8), dim3(256), 0, s, il.T, chunk, il.gx, W, H, ranges, point_list, recs, out_color, \
 	                   out_depth, out_median, out_opacity, final_T, n_contrib, med_pos, ctl, cap, max_sorted, tile_order, staged_out)
-#ifdef GSR_AB_VARIANTS
-	if (wave_lists) {
-		const GsCtl* ctl = ctl_;
-		if (nocull) GSR_LAUNCH_FWD(composite_fwd_kernel<true>);
-		else GSR_LAUNCH_FWD(composite_fwd_kernel<false>);
-	} else
-#endif
-	{   // (a build without GSR_AB_VARIANTS refuses fwd_variant 1 in gsr_forward: wave_lists is false here)
-		GsCtl* ctl = ctl_;
-		if (fast_exp) {
-			if (nocull) GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<true, true>));
-			else GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<false, true>));
-		} else {
-			if (nocull) GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<true, false>));
-			else GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<false, false>));
-		}
+	if (fast_exp) {
+		if (nocull) GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<true, true>));
+		else GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<false, true>));
+	} else {
+		if (nocull) GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<true, false>));
+		else GSR_LAUNCH_FWD((composite_fwd_quarter_kernel<false, false>));
 	}
 #undef GSR_LAUNCH_FWD
 }

@@ -66,15 +66,6 @@ def resolved():
     if cur[i] < 0:
         from . import _C
         cur[i] = int(_C.get_option("fast_exp"))
-        # fast_exp merely inherited from the process default (on since round 4), together with an A/B kernel variant that has
-        # no v_exp_f32 form (per-wave lists: fwd_variant 1, bwd_variant bit 1): the variant wins, the call runs in the
-        # reproducible mode -- asking for BOTH explicitly stays an error of the library
-        if cur[i]:
-            fv, bv = cur[FIELDS.index("fwd_variant")], cur[FIELDS.index("bwd_variant")]
-            fv = int(_C.get_option("fwd_variant")) if fv < 0 else fv
-            bv = int(_C.get_option("bwd_variant")) if bv < 0 else bv
-            if fv == 1 or (bv >= 0 and (bv & 2)):
-                cur[i] = 0
     return tuple(cur)
 
 

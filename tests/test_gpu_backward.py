@@ -19,7 +19,7 @@ import torch
 
 from gaustudio_amd import scenes
 
-from util import ab_variants, assert_bits_equal, hip_backward_raw, hip_forward, oracle_forward, scene_kwargs, to_np
+from util import assert_bits_equal, hip_backward_raw, hip_forward, oracle_forward, scene_kwargs, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -125,8 +125,8 @@ def test_null_upstream_gradients_equal_explicit_zeros(oracle, fast_exp):
     """include/gsrast.h gsr_backward: each of the four upstream image gradients may be NULL = "the loss does not use that
     output" = zero; nothing is loaded for it.  Every output (and the composite-stage sums) must be BIT-equal to the call with
     explicit zero planes -- for every subset, in both exp modes, in the short- and the long-list regime, with a non-black
-    background, through the per-quarter kernels (colour alone: the CONLY instantiation) and the per-wave A/B kernel -- and the
-    explicit-zero call is held against the oracle as every other backward is."""
+    background, through the general kernel and (colour alone) the CONLY instantiation -- and the explicit-zero call is held
+    against the oracle as every other backward is."""
     import gaustudio_amd
     cases = [(scenes.make_camera(333, 211), dict(seed=4, sigma_px_median=3.0), 6000, None),
              (scenes.make_camera(96, 64), dict(seed=5, sigma_px_median=9.0), 9000, torch.tensor([1.0, 0.5, 0.25]))]   # long lists: row flags
@@ -140,7 +140,7 @@ def test_null_upstream_gradients_equal_explicit_zeros(oracle, fast_exp):
             for keep in ((1, 0, 0, 0), (1, 1, 0, 0), (0, 0, 1, 0), (0, 1, 1, 1), (1, 0, 0, 1), (0, 0, 0, 0)):
                 dense = [g if k else z for g, z, k in zip(full, zeros, keep)]
                 sparse = [g if k else None for g, k in zip(full, keep)]
-                for variant in ({}, dict(bwd_variant=2)) if (not fast_exp and ab_variants()) else ({},):
+                for variant in ({},):
                     a = hip_backward_raw(hs, sc, cam, 3, kw, dense, bg=bg, options=dict(variant))
                     b = hip_backward_raw(hs, sc, cam, 3, kw, sparse, bg=bg, options=dict(variant))
                     for k in GRAD_KEYS + ("acc",):
@@ -276,10 +276,10 @@ def test_backward_on_adversarial_scenes(oracle, kind):
 
 def test_backward_variants_of_the_kernel_agree():
     """composite_bwd carries dead pixels through arithmetically (G masked to 0, 1/(1-0) == 1); the variant that keeps
-    an explicit select on T must give the same bits.  The per-wave (8x8) kernel of round 2a (variant bit 1) and a run
-    on the reference's square binning (the extra instances contribute exact zeros, but shift the 64-instance batches
-    and with them the order in which the quarters of a wave meet in an instance) add the same terms in another order:
-    equal within the fp32 summation tolerance of every tensor's scale."""
+    an explicit select on T must give the same bits.  Variant bit 1 (a per-wave kernel the library no longer has) is
+    refused.  A run on the reference's square binning (the extra instances contribute exact zeros, but shift the
+    staged batches and with them the order in which the quarters of a wave meet in an instance) adds the same terms
+    in another order: equal within the fp32 summation tolerance of every tensor's scale."""
     from gaustudio_amd import _C
     cam = scenes.make_camera(640, 360)
     sc = scenes.make_scene(120000, cam, seed=12)
@@ -291,21 +291,13 @@ def test_backward_variants_of_the_kernel_agree():
     try:
         _C.set_option("bwd_variant", 1)
         b = hip_backward_raw(hs, sc, cam, 3, kw, grads)
-        w0 = w1 = None
-        if ab_variants():
-            _C.set_option("bwd_variant", 2)
-            w0 = hip_backward_raw(hs, sc, cam, 3, kw, grads)
-            _C.set_option("bwd_variant", 3)
-            w1 = hip_backward_raw(hs, sc, cam, 3, kw, grads)
-        else:         # the shipped build refuses the per-wave kernel loudly
-            _C.set_option("bwd_variant", 2)
-            with pytest.raises(RuntimeError, match="not in this build"):
-                hip_backward_raw(hs, sc, cam, 3, kw, grads)
+        _C.set_option("bwd_variant", 2)
+        with pytest.raises(RuntimeError, match="not in this build"):
+            hip_backward_raw(hs, sc, cam, 3, kw, grads)
     finally:
         _C.set_option("bwd_variant", old)
     for k in GRAD_KEYS + ("acc",):
         assert torch.equal(a[k], b[k]), k
-        assert w0 is None or torch.equal(w0[k], w1[k]), k
     try:
         _C.set_option("tight_binning", 0)
         hs0 = hip_forward(sc, cam, 3, kw)
@@ -313,17 +305,7 @@ def test_backward_variants_of_the_kernel_agree():
     finally:
         _C.set_option("tight_binning", 1)
     assert hs0["num_binned"] > hs["num_binned"]
-    # the default backward takes its per-block cull from the masks composite_fwd left behind the lists; after a forward
-    # that leaves none (per-wave walk) it computes its own, slightly different conservative masks: same live terms
-    d = None
-    if ab_variants():
-        try:
-            _C.set_option("fwd_variant", 1)
-            hs1 = hip_forward(sc, cam, 3, kw)
-            d = hip_backward_raw(hs1, sc, cam, 3, kw, grads)
-        finally:
-            _C.set_option("fwd_variant", 0)
-    for other in [o for o in (w0, c, d) if o is not None]:
+    for other in (c,):
         for k in GRAD_KEYS + ("acc",):
             x, y = a[k].double(), other[k].double()
             if x.numel() == 0:

@@ -11,7 +11,7 @@ import torch
 
 from gaustudio_amd import scenes
 
-from util import ab_variants, compare_forward_exact, hip_forward, oracle_forward, scene_kwargs, to_np
+from util import compare_forward_exact, hip_forward, oracle_forward, scene_kwargs, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -295,26 +295,22 @@ def test_culling_and_tight_binning_change_no_bit(P, W, H, D):
 @pytest.mark.parametrize("P,W,H,D,sig", [(20000, 400, 400, 3, None), (30000, 333, 217, 1, 6.0), (3000, 131, 77, 0, 25.0),
                                          (1_000_000, 1920, 1080, 3, None)], ids=["small", "odd", "wide", "C3"])
 def test_forward_variants_agree_bit_for_bit(P, W, H, D, sig):
-    """composite_fwd with per-quarter (4x4) instance lists (default) against the per-wave (8x8) walk and against the
-    walk without any culling: every output and the per-pixel state are bit-identical (image sizes that are not
-    multiples of 16 or 4 included: clipped quarters)."""
+    """composite_fwd with per-quarter (4x4) instance lists (default) against the walk without any culling: every
+    output and the per-pixel state are bit-identical (image sizes that are not multiples of 16 or 4 included:
+    clipped quarters)."""
     cam = scenes.make_camera(W, H)
     sc = scenes.make_scene(P, cam, seed=1, **({} if sig is None else {"sigma_px_median": sig}))
     kw = scene_kwargs(sc, True, False)
     a = hip_forward(sc, cam, D, kw)
-    b = None
-    if ab_variants():
-        with _with_options(fwd_variant=1):
-            b = hip_forward(sc, cam, D, kw)
     with _with_options(cull=0):
         c = hip_forward(sc, cam, D, kw)
-    for other in [o for o in (b, c) if o is not None]:
+    for other in (c,):
         for k in ("color", "depth", "median", "opacity", "radii", "final_T", "n_contrib", "point_list", "ranges"):
             assert torch.equal(a[k], other[k]), k
 
 
 def _adversarial_scene(P, cam, seed, kind):
-    """Scenes aimed at the conservative block culls (gs_quarter_mask / gs_box_may_touch / gs_tight_rect): needles
+    """Scenes aimed at the conservative block culls (gs_quarter_mask / gs_tight_rect): needles
     (axis ratios up to 1:300, every orientation), pancakes seen edge-on, screen-filling blobs, opacities hugging the
     1/255 visibility threshold and the 0.99 alpha clamp, and centres sitting on block and tile borders."""
     g = torch.Generator().manual_seed(seed)
@@ -347,22 +343,18 @@ def _adversarial_scene(P, cam, seed, kind):
 
 @pytest.mark.parametrize("kind", ["needles", "pancakes", "blobs", "threshold", "borders"])
 def test_block_culls_are_conservative_on_adversarial_scenes(oracle, kind):
-    """The per-quarter walk (default), the per-wave walk and the walk without any culling give the same bits on scenes
-    built to stress the culls; the default is also compared with the CPU oracle (which has no cull at all)."""
+    """The per-quarter walk (default) and the walk without any culling give the same bits on scenes built to stress
+    the culls; the default is also compared with the CPU oracle (which has no cull at all)."""
     W, H = 331, 203
     cam = scenes.make_camera(W, H)
     sc = _adversarial_scene(6000 if kind != "blobs" else 1500, cam, seed=31, kind=kind)
     kw = scene_kwargs(sc, True, False)
     a = hip_forward(sc, cam, 2, kw)
-    b = None
-    if ab_variants():
-        with _with_options(fwd_variant=1):
-            b = hip_forward(sc, cam, 2, kw)
     with _with_options(cull=0):
         c = hip_forward(sc, cam, 2, kw)
     with _with_options(cull=0, tight_binning=0):
         d = hip_forward(sc, cam, 2, kw)
-    for other in [o for o in (b, c, d) if o is not None]:
+    for other in (c, d):
         for k in ("color", "depth", "median", "opacity", "radii", "final_T"):
             assert torch.equal(a[k], other[k]), (kind, k)
     compare_forward_exact(a, oracle_forward(oracle, sc, cam, 2, kw))

@@ -5,7 +5,7 @@
 # On the GPU box: tools/with_variant.sh NAME <command ...> swaps it in for the duration of the command.
 set -euo pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
-NAME="$1"; FWD="${2:-}"; BWD="${3:-}"; ALL="${4:-}"    # ALL: make variables for every file, e.g. "AB=1" (nothing is reused then)
+NAME="$1"; FWD="${2:-}"; BWD="${3:-}"; ALL="${4:-}"    # ALL: make variables for every file, e.g. "EXTRA=-DGSR_PRE_COOP=0" (nothing is reused then)
 SRC="$ROOT/gaustudio_amd/csrc"
 OUT="$ROOT/gpurun_variants"
 TMP="$(mktemp -d /tmp/gsrvar.XXXXXX)"

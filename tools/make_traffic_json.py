@@ -61,9 +61,7 @@ doc = {"_comment": "per-launch counters of the benchmark-sized dispatches (large
                    "factors calibrated in profiles/r02_fetch_write_calibration.txt for these kernels' access patterns (64-B record "
                    "gather: 1.0), traffic_upper_bytes = 2*FETCH + WRITE (the coalesced-stream factor applied to every read)",
        "workload": wl}
-# (the per-quarter compositing kernels are the default ones; the per-wave variants only show up in A/B runs)
-for name in ("composite_fwd_quarter_kernel", "composite_bwd_quarter_kernel", "composite_fwd_kernel", "composite_bwd_kernel",
-             "preprocess_fwd_kernel", "preprocess_bwd_kernel", "preprocess_bwd_sh_coop_kernel", "bin_chunk_kernel",
+for name in ("composite_fwd_quarter_kernel", "composite_bwd_quarter_kernel", "preprocess_fwd_kernel", "preprocess_bwd_kernel", "preprocess_bwd_sh_coop_kernel", "bin_chunk_kernel",
              "tile_sort_kernel"):
     grids = [g for (n, g) in sq if n == name]
     if not grids:

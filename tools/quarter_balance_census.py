@@ -32,7 +32,7 @@ BATCH, U = 128, 4
 
 
 def box_test(xy, co, bx0, by0, bx1, by1):
-    """The kernels' conservative block test (gs_quarter_mask / gs_box_may_touch), as in tools/scene_stats.py."""
+    """The kernels' conservative block test (gs_quarter_mask, as a box test), as in tools/scene_stats.py."""
     ha, nb, hc = -0.5 * co[:, 0], -co[:, 1], -0.5 * co[:, 2]
     pcut = torch.clamp_min(-torch.log(255.0 * co[:, 3]) - 0.001, -80.0)
     X0, X1 = xy[:, 0] - bx1, xy[:, 0] - bx0

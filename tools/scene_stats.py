@@ -44,7 +44,7 @@ for t in tiles.tolist():
 print(f"(tile,instance) with any live pixel in the 16x16 tile: {tot_tilehit / tot_inst:.3f}")
 print(f"sampled {len(tiles)} tiles: instances {tot_inst}; (block,instance) with any live pixel: {tot_blockhit / (4 * tot_inst):.3f}; live (pixel,instance) pairs: {tot_live / tot_pairs:.4f}")
 
-# ---- how tight is the kernel's conservative box test (gs_box_may_touch) compared with the exact "any live pixel"? ----
+# ---- how tight is a conservative closed-form box test (the kind of cull gs_quarter_mask applies per 4x4 block) compared with the exact "any live pixel"? ----
 def box_test(xy, co, bx0, by0, bx1, by1):
     ha, nb, hc = -0.5 * co[:, 0], -co[:, 1], -0.5 * co[:, 2]
     pcut = torch.clamp_min(-torch.log(255.0 * co[:, 3]) - 0.001, -80.0)

@@ -19,6 +19,8 @@ from .scaffold import (ScaffoldGaussians, ScaffoldModel, decode, decode_torch, r
 from .losses import l1_loss, photometric_loss, photometric_loss_with_parts, ssim, ssim_map  # noqa: F401,E402
 # the optimiser half of training: a one-launch (visibility-sparse) Adam and adaptive density control
 from .optim import DensifyReport, DensityControl, GaussianAdam  # noqa: F401,E402
+# Scaffold-GS anchor control: grow anchors by voxel level, prune them, carry a torch Adam's moments
+from .anchor_control import AnchorControl, AnchorReport  # noqa: F401,E402
 # the geometric regularisers of 2D Gaussian surfel training: normal consistency + depth distortion on the surfel allmap
 from .surfel_losses import (intrinsics_from_settings, surfel_geometric_loss, surfel_geometric_loss_with_parts,  # noqa: F401,E402
                             surfel_maps)

@@ -1062,6 +1062,75 @@ typedef struct gsr_compact_group {
 int gsr_densify_emit(int num_rows, int n_split, const gsr_compact_group* groups, int num_groups, const int* pos,
                      const float* noise, const float* scaling, const float* rotation, void* stream);
 
+/* ---- Scaffold-GS anchor control: the statistics, anchor growing by voxel level and pruning as one compaction that carries
+ * the Adam moments (csrc/gsr_anchor.hip).  Additive to ABI 6.  Contract to the bit: INTEGRATION.md s23b (its definition:
+ * tests/anchor_model.py); design: DESIGN.md s20b.  Every tensor: device, 4-byte elements, contiguous.  0 <= num_anchors
+ * <= 2^24, 1 <= k <= 16 (GSR_ERR_ARG otherwise).  No float atomics: bit-identical from run to run and on any stream. ---- */
+#define GSR_ERR_CELL (-7)        /* gsr_anchor_level: a candidate's position is not finite or its cell does not fit 21 bits */
+#define GSR_ANCHOR_FEAT 32       /* floats of an anchor_feat row */
+#define GSR_ANCHOR_MAX_LEVELS 8  /* levels of one pass */
+
+/* One launch.  Gaussian m < num_gaussians with radii[m] > 0: slot = anchor_index[m] k + offset_index[m] gets offset_grad_accum
+ * += sqrt(gx gx + gy gy) of viewspace_grad [num_gaussians,3] and offset_denom += 1.  Anchor a with visible[a] (u8): anchor_denom
+ * += 1.  The first Gaussian of an anchor's run (runs are contiguous, anchor-major): opacity_accum[a] += the f32 sum of the run's
+ * opacities in order.  A Gaussian whose indices are out of range is skipped.  No wait. */
+int gsr_anchor_accumulate(int num_anchors, int k, int num_gaussians, const int* anchor_index, const int* offset_index,
+                          const float* opacity, const float* viewspace_grad, const int* radii, const unsigned char* visible,
+                          float* offset_grad_accum, int* offset_denom, float* opacity_accum, int* anchor_denom, void* stream);
+
+/* The new anchors of an earlier level of the same pass (HOST): their cells (device, int32 [count,3]) and the voxel size they
+ * were formed with; their positions are f32(cell) * cur. */
+typedef struct gsr_anchor_cells {
+	const int* cells;
+	int count;
+	float cur;
+} gsr_anchor_cells;
+
+/* One level of growing.  A slot (a, j) is a candidate when offset_denom > mature_min, avg = accum / f32(denom) >= grad_min and
+ * rand [num_anchors k] > rand_min.  Its position is anchor + offset * gs_exp(clamp(scale_raw[a, 0:3], -80, 80)), its cell
+ * rintf(position / cur).  The new anchors of the level are the distinct candidate cells that hold neither one of the
+ * num_anchors anchors nor one of prior[num_prior] (cells formed the same way, at this level's cur), in ascending (x, y, z)
+ * order.  The allocator is called up to three times: scratch twice, then ONE block that the caller keeps until its emit: the
+ * cells int32 [count,3] at *cells_out and, behind them, the per-cell maximum of the candidates' anchor_feat rows, f32
+ * [count,32], at *feat_out (both NULL when count is 0).  info_host[2] (HOST) = {candidates, count}.  Waits on `stream` twice:
+ * for the candidate count with the cell range (the sort's key width comes from it), and for the count.  GSR_ERR_CELL, nothing
+ * allocated for the caller, for a candidate out of range. */
+int gsr_anchor_level(gsr_alloc_fn workspace_alloc, void* workspace_ctx, int num_anchors, int k, const float* anchor,
+                     const float* offset, const float* scale_raw, const float* anchor_feat, const float* offset_grad_accum,
+                     const int* offset_denom, const float* rand, int mature_min, float grad_min, float rand_min, float cur,
+                     const gsr_anchor_cells* prior, int num_prior, int** cells_out, float** feat_out, long long* info_host,
+                     void* stream);
+
+/* The prune decision and its scan: pos (device, int32 [num_anchors + 1]) = exclusive scan of "anchor a survives", i.e. not
+ * (anchor_denom > settled_min and opacity_accum < min_opacity * f32(anchor_denom)).  *survivors_host (HOST) = pos[num_anchors].
+ * Waits on `stream` once.  Scratch from the allocator callback, once. */
+int gsr_anchor_prune(gsr_alloc_fn workspace_alloc, void* workspace_ctx, int num_anchors, const float* opacity_accum,
+                     const int* anchor_denom, int settled_min, float min_opacity, int* pos, int* survivors_host, void* stream);
+
+/* One tensor of gsr_anchor_emit (HOST): `width` 4-byte words per anchor.  kind: 0 a parameter or a moment (copied),
+ * 1 offset_grad_accum / offset_denom (0 where offset_denom > mature_min, when mature_min >= 0), 2 opacity_accum / anchor_denom
+ * (0 where anchor_denom > settled_min). */
+typedef struct gsr_anchor_tensor {
+	const void* src;
+	void* dst;
+	int width;
+	int kind;
+} gsr_anchor_tensor;
+
+#define GSR_ANCHOR_COPY 0
+#define GSR_ANCHOR_SLOT_STAT 1
+#define GSR_ANCHOR_ANCHOR_STAT 2
+#define GSR_ANCHOR_MAX_TENSORS 19   /* five parameters with two moments each and four statistics */
+
+/* The one write of every output tensor.  Survivor a of pos goes to row pos[a] of every tensors[t].dst, its statistics reset as
+ * their kind says.  The new anchors of
+ * levels[num_levels] follow in level order from row pos[num_anchors]: tensors[0 .. 4] are anchor, anchor_feat, offset,
+ * scale_raw, rot_raw and get f32(cell) * cur, the level's feature rows (feat[l]: device, f32 [count,32]), 0, f32(log(cur))
+ * six times and (1, 0, 0, 0); every further tensor gets 0.  Sources are never written.  No wait. */
+int gsr_anchor_emit(int num_anchors, int k, const gsr_anchor_tensor* tensors, int num_tensors, const int* pos,
+                    const int* offset_denom, const int* anchor_denom, int mature_min, int settled_min,
+                    const gsr_anchor_cells* levels, const float* const* feat, int num_levels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
